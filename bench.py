@@ -11,6 +11,13 @@ is rank-sharded and all-gathered over RCCL/xGMI each generation.
 
 Run: python bench.py [--gpus N] [--steps K] [--warmup W]
 Distributed: torchrun --nnodes=1 --nproc-per-node N bench.py --gpus N ...
+
+A plain run only sets up, warms up, times the K steps and prints the JSON
+result line. --dump-outputs DIR additionally writes what the last timed
+step returned (x_res, y_res, hv) as DIR/<name>.npy; the inputs are seeded,
+so two builds can be compared output for output. Everything else the
+benchmark measures (the bf16-vs-fp32 accuracy block of --dtype bf16) runs
+only with --full.
 """
 
 from __future__ import annotations
@@ -112,6 +119,18 @@ def one_epoch(X, Y, pop, rank, world, device, seed, n_gen=N_GEN, compute="fp32")
     return x_res, y_res, hv
 
 
+def dump_outputs(out_dir, x_res, y_res, hv):
+    """Write one_epoch's return values as <out_dir>/<name>.npy (float32 /
+    float64, a few KB): the resample batch, its real objective values and
+    the batch's hypervolume."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "x_res.npy"),
+            x_res.detach().cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "y_res.npy"),
+            y_res.detach().cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "hv.npy"), np.asarray([float(hv)], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -121,7 +140,14 @@ def main():
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"])
     ap.add_argument("--pop-per-gpu", type=int, default=POP_PER_GPU,
                     help="diagnostic override of the per-GPU population")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the untimed extras (bf16 accuracy delta "
+                         "vs fp32 with --dtype bf16)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     compute = "bf16" if args.dtype == "bf16" else "fp32"
 
     rank, world = comm.init_from_env()
@@ -142,7 +168,7 @@ def main():
         if device.type == "cuda":
             torch.cuda.synchronize()
 
-    hv = None
+    x_res = y_res = hv = None
     for w in range(args.warmup):
         one_epoch(X, Y, pop, rank, world, device, seed=100 + w, n_gen=args.gens,
                   compute=compute)
@@ -150,13 +176,16 @@ def main():
     barrier_sync()
     t0 = time.perf_counter()
     for s in range(args.steps):
-        _, _, hv = one_epoch(X, Y, pop, rank, world, device, seed=200 + s,
-                             n_gen=args.gens, compute=compute)
+        x_res, y_res, hv = one_epoch(X, Y, pop, rank, world, device, seed=200 + s,
+                                     n_gen=args.gens, compute=compute)
     barrier_sync()
     t1 = time.perf_counter()
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, x_res, y_res, hv)
+
     accuracy = None
-    if compute == "bf16" and rank == 0 and device.type == "cuda":
+    if args.full and compute == "bf16" and rank == 0 and device.type == "cuda":
         # untimed accuracy delta vs fp32: same seed => identical theta (the
         # search is fp32 in both modes), so the delta isolates the bf16
         # posterior path (cross kernel + Cholesky trailing updates)

@@ -190,6 +190,35 @@ def test_bench_json_contract():
     assert "synthetic" in d["data"]
 
 
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes the last timed step's return values as float
+    .npy files consistent with the JSON line; --steps sets the number of
+    timed steps; --full is accepted and keeps the same contract."""
+    import json
+    import subprocess
+    import sys as _sys
+
+    out_dir = tmp_path / "dump"
+    out = subprocess.run(
+        [_sys.executable, "bench.py", "--steps", "2", "--warmup", "0", "--gens", "2",
+         "--full", "--dump-outputs", str(out_dir)],
+        capture_output=True, text=True, timeout=600,
+        cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+    )
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads(out.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 2 and d["value"] == d["ms_per_step"] > 0
+    assert sorted(p.name for p in out_dir.iterdir()) == ["hv.npy", "x_res.npy", "y_res.npy"]
+    x_res = np.load(out_dir / "x_res.npy")
+    y_res = np.load(out_dir / "y_res.npy")
+    hv = np.load(out_dir / "hv.npy")
+    assert x_res.dtype == np.float32 and x_res.shape == (50, 30)
+    assert y_res.dtype == np.float64 and y_res.shape == (50, 2)
+    assert hv.dtype == np.float64 and hv.shape == (1,)
+    assert np.isfinite(x_res).all() and np.isfinite(y_res).all()
+    assert float(hv[0]) == d["config"]["final_hypervolume_ref11"]
+
+
 @pytest.mark.parametrize("mod", ["analyze", "train", "onestep"])
 def test_cli_help_runs(mod):
     import subprocess
