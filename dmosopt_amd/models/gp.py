@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from dmosopt_amd import ops
-from dmosopt_amd.models.gp_core import FittedGP, batched_nmll
+from dmosopt_amd.models.gp_core import FittedGP, _nmll_bind_enabled, batched_nmll
 from dmosopt_amd.models.sceua import sceua_batched
 
 
@@ -149,10 +149,24 @@ class _GPRBase:
         if optimizer in ("sceua", "dlib", None):
             YnT = Yn.T.contiguous()  # (m, N)
 
+            # gathered per-row targets, cached per stream-id tensor: SCE-UA
+            # passes the SAME tensor object on every stage call, so the
+            # gather runs once per fit instead of once per call, and the
+            # NMLL graph sees the same y tensor and skips its input copy
+            y_rows: dict = {}
+
+            def rows_for(stream: torch.Tensor) -> torch.Tensor:
+                if not _nmll_bind_enabled():
+                    return YnT[stream]
+                hit = y_rows.get(id(stream))
+                if hit is None or hit[0] is not stream or hit[1] != stream._version:
+                    hit = y_rows[id(stream)] = (stream, stream._version, YnT[stream])
+                return hit[2]
+
             def nmll_func(theta_batch: torch.Tensor, stream: torch.Tensor):
                 # one fused batched call for ALL streams: per-row y targets
                 return batched_nmll(
-                    X, YnT[stream], theta_batch.to(self.dtype),
+                    X, rows_for(stream), theta_batch.to(self.dtype),
                     nu=self.nu, anisotropic=anisotropic,
                 )
 

@@ -347,6 +347,28 @@ def chol_factor_batched(K):
     return L, logdet, info
 
 
+CHOL_SCHEDULES = {"classic": 0, "lookahead": 1}
+
+
+def chol_factor_multik(K, rhs=None, schedule="classic"):
+    """Multi-launch factorization of K (B,N,N) with an EXPLICIT trailing-
+    update schedule ("classic" or "lookahead") and an optional rhs (B,N)
+    carried through the fused forward solve.
+
+    Returns (L, logdet (B,), info (B,), z) with z = L^-1 rhs (None without
+    rhs); the inputs are left untouched. The DMOSOPT_CHOL_* switches are
+    latched once per process, so this is how the two schedules are compared
+    inside one process. Native only: a missing extension is an error."""
+    if not (_use_native(K) and K.dtype == torch.float32):
+        raise RuntimeError("chol_factor_multik needs the native extension "
+                           "and a float32 GPU tensor")
+    L = K.contiguous().clone()
+    z = None if rhs is None else rhs.contiguous().float().clone()
+    logdet, info = _native.cholesky_multik_sched_(
+        L, z, CHOL_SCHEDULES[schedule])
+    return L, logdet, info, z
+
+
 def chol_solve_batched(L, Y):
     """Solve K X = Y given the factor L (B,N,N); Y (B,N,R) -> X (B,N,R)."""
     if _use_native(L) and L.dtype == torch.float32:

@@ -17,6 +17,8 @@ void launch_matern_assemble(const float*, const float*, const float*, float*,
                             int, int, int, int, int, float, int, int, int,
                             hipStream_t);
 void launch_cholesky_batched(float*, float*, int*, int, int, hipStream_t);
+void launch_cholesky_multik_sched(float*, float*, int*, float*, int, int, int,
+                                  hipStream_t);
 int launch_cholesky_fused_solve(float*, float*, int*, float*, int*, int,
                                 int, hipStream_t);
 void launch_forward_solve_batched(const float*, float*, int, int, int,
@@ -365,6 +367,36 @@ std::vector<torch::Tensor> cholesky_batched_(torch::Tensor A) {
   auto info = torch::zeros({B}, A.options().dtype(torch::kInt32));
   launch_cholesky_batched(A.data_ptr<float>(), logdet.data_ptr<float>(),
                           info.data_ptr<int>(), B, N, cur_stream());
+  return {logdet, info};
+}
+
+// Multi-launch factorization with an EXPLICIT trailing-update schedule
+// (0 = classic panel + SYRK launches, 1 = look-ahead step launches) and an
+// optional rhs (B, N) carried through the fused forward solve. The env
+// switches are latched per process, so this is the only way to compare the
+// two schedules inside one process. In place: A -> L, rhs -> L^-1 rhs.
+std::vector<torch::Tensor> cholesky_multik_sched_(
+    torch::Tensor A, c10::optional<torch::Tensor> rhs, int64_t sched) {
+  CHECK_GPU(A);
+  TORCH_CHECK(A.dim() == 3 && A.size(1) == A.size(2), "A must be (B, N, N)");
+  TORCH_CHECK(A.scalar_type() == torch::kFloat32 && A.is_contiguous(),
+              "A must be contiguous float32");
+  TORCH_CHECK(sched == 0 || sched == 1, "sched must be 0 or 1");
+  const int B = A.size(0), N = A.size(1);
+  float* rhs_ptr = nullptr;
+  if (rhs.has_value()) {
+    const torch::Tensor& r = rhs.value();
+    CHECK_GPU(r);
+    TORCH_CHECK(r.dim() == 2 && r.size(0) == B && r.size(1) == N,
+                "rhs must be (B, N)");
+    TORCH_CHECK(r.scalar_type() == torch::kFloat32, "rhs must be float32");
+    rhs_ptr = r.data_ptr<float>();
+  }
+  auto logdet = torch::empty({B}, A.options());
+  auto info = torch::zeros({B}, A.options().dtype(torch::kInt32));
+  launch_cholesky_multik_sched(A.data_ptr<float>(), logdet.data_ptr<float>(),
+                               info.data_ptr<int>(), rhs_ptr, B, N, (int)sched,
+                               cur_stream());
   return {logdet, info};
 }
 
@@ -946,6 +978,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gp_nmll", &gp_nmll, "Fused batched GP NMLL (assemble+chol+solve+reduce)");
   m.def("cholesky_batched_", &cholesky_batched_,
         "In-place batched Cholesky; returns (logdet, info)");
+  m.def("cholesky_multik_sched_", &cholesky_multik_sched_,
+        "In-place multi-launch Cholesky with an explicit schedule "
+        "(0 classic, 1 look-ahead) and optional fused rhs; returns "
+        "(logdet, info)",
+        py::arg("A"), py::arg("rhs") = py::none(), py::arg("sched") = 0);
   m.def("forward_solve_", &forward_solve_, "In-place batched L z = y solve");
   m.def("backward_solve_", &backward_solve_, "In-place batched L^T x = z solve");
   m.def("dominance_degree_matrix", &dominance_degree_matrix);

@@ -246,18 +246,116 @@ __global__ __launch_bounds__(CHOL_TPB) void cholesky_batched_kernel(
 #define CHOLP_TPB 256
 #define SYRK_TS 64  // trailing-update tile edge
 
+// Shared arithmetic of the rank-32 trailing update. EVERY path that applies
+// a panel's update — the SYRK tile kernel, the persistent kernel's tiles and
+// both roles of the look-ahead step kernel — goes through these two inlines,
+// so an output element's value cannot depend on which block, tile origin or
+// schedule computed it (NOTES.md -ffp-contract rule: one inline per chain).
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+
+// One 16x16 sub-tile: acc = 0, then v_mfma_f32_16x16x4_f32 over k = 0..28.
+// arow / brow point at this lane's operand rows (A[i][.] and B[.][j] =
+// P[j][.]) in LDS; aswz / bswz are the rows' XOR swizzles (0 = unswizzled).
+// The caller subtracts acc from the element it owns (operand map in
+// chol_syrk_kernel's comment).
+__device__ __forceinline__ f32x4 chol_subtile_acc(const float* arow, int aswz,
+                                                  const float* brow, int bswz,
+                                                  int lk) {
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int k = 0; k < CHOL_BS; k += 4) {
+    const float a = arow[(k + lk) ^ aswz];
+    const float b = brow[(k + lk) ^ bswz];
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
+  }
+  return acc;
+}
+
+// One rhs entry of the fused forward solve: the 32-step fmaf chain in t
+// order against the panel's solved segment z.
+__device__ __forceinline__ float chol_rhs_row_update(const float* prow,
+                                                     int swz,
+                                                     const float* z,
+                                                     float acc) {
+#pragma unroll
+  for (int t = 0; t < CHOL_BS; ++t) acc = fmaf(-prow[t ^ swz], z[t], acc);
+  return acc;
+}
+
+// Look-ahead role A, strip part: rows [c0, c0+rows) of the 32-column strip
+// at k0 receive the PREVIOUS panel's update in place in the TRSM staging
+// buffer: on exit P[r][0..31] holds the updated strip row
+// A[c0+r][k0..k0+31] - acc, ready for the TRSM. Lj holds the previous
+// panel's rows k0..k0+31 (swizzled, published by a block barrier before the
+// call). Wave w of nw takes the 16-row groups w, w+nw, ...; it stages the
+// previous panel's rows of a group into P itself (coalesced, zero beyond
+// `rows`), multiplies, and overwrites them with the result. A group's rows
+// are touched by that one wave only, so there is no block barrier inside
+// and wave 0 never waits for this staging. P keeps its +1-padded layout
+// instead of the SYRK tiles' swizzle so the update can land in place (a
+// separate swizzled copy of up to TPB rows would push the static LDS past
+// 64 KB); the operand read is 2-way bank-conflicted at worst.
+__device__ __forceinline__ void chol_strip_rows(
+    const float* __restrict__ Ab, int N, int k0, int c0, int rows,
+    float (*P)[CHOL_BS + 1], float (*Lj)[CHOL_BS], int w, int nw) {
+  const int lane = threadIdx.x & 63;
+  const int lr = lane & 15, lk = lane >> 4;
+  const int ngroups = (rows + 15) / 16;
+  const int kp = k0 - CHOL_BS;
+  for (int g = w; g < ngroups; g += nw) {
+    const int r16 = g * 16;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {  // 16 rows x 32 columns, 2 rows per pass
+      const int rr = r16 + q * 2 + (lane >> 5), c = lane & 31;
+      P[rr][c] = (rr < rows) ? Ab[(long long)(c0 + rr) * N + kp + c] : 0.0f;
+    }
+    __threadfence_block();  // staged rows cross lanes inside the wave
+    float a0[4], a1[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int rr = r16 + lk * 4 + r;
+      const bool ok = rr < rows;
+      const float* src = Ab + (long long)(c0 + rr) * N + k0 + lr;
+      a0[r] = ok ? src[0] : 0.0f;
+      a1[r] = ok ? src[16] : 0.0f;
+    }
+    const int rb1 = 16 + lr;
+    const f32x4 acc0 =
+        chol_subtile_acc(P[r16 + lr], 0, Lj[lr], (lr & 7) << 2, lk);
+    const f32x4 acc1 =
+        chol_subtile_acc(P[r16 + lr], 0, Lj[rb1], (rb1 & 7) << 2, lk);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int rr = r16 + lk * 4 + r;
+      if (rr < rows) {
+        P[rr][lr] = a0[r] - acc0[r];
+        P[rr][16 + lr] = a1[r] - acc1[r];
+      }
+    }
+  }
+}
+
 // Factor the 32x32 diagonal block at (k0,k0) and panel-solve the rows below
 // it. One block per matrix; also accumulates the step's logdet contribution
 // deterministically (no atomics: k-steps are stream-ordered).
 // Device body shared by the per-step panel kernel and the persistent
 // whole-factorization kernel (chol_persist_kernel): identical arithmetic,
 // only the launch wrapper differs.
-template <int GROUP_COLS, int TPB>
+//
+// PRE = true is the look-ahead schedule's role A (chol_step_kernel): the
+// previous panel's rank-32 update has been applied everywhere EXCEPT this
+// panel's own strip (rows >= k0, columns k0..k0+bs-1) and rhs segment, so
+// the body first applies it there — through the shared inlines above, so
+// each element sees the arithmetic the SYRK tile would have given it — and
+// then proceeds exactly as the plain panel. Lj ([33][32]) stages the
+// previous panel's rows k0..k0+31 (swizzled) and, in row 32, its solved rhs
+// segment; unused (nullptr) when PRE is false.
+template <int GROUP_COLS, int TPB, bool PRE = false>
 __device__ __forceinline__ void chol_panel_body(
     float* __restrict__ Ab, float* __restrict__ logdet_b,
     int* __restrict__ info_b, int N, int k0, float* __restrict__ rhs_b,
     float (*S)[CHOL_BS + 1], float (*colbuf4)[CHOL_BS],
-    float (*P)[CHOL_BS + 1]) {
+    float (*P)[CHOL_BS + 1], float (*Lj)[CHOL_BS] = nullptr) {
   // rhs != nullptr: FUSED FORWARD SOLVE (bordered-matrix scheme). rhs (B, N)
   // starts as y and finishes as z = L^-1 y without a separate TRSV kernel:
   // this panel solves entries [k0, k0+bs) against the factored diagonal
@@ -276,9 +374,12 @@ __device__ __forceinline__ void chol_panel_body(
   // coalesced stage of the block into LDS by the whole workgroup first —
   // a single wave doing the 32x32 global load directly issues ~1000
   // uncoalesced (1200 B stride) loads and stalls on memory latency
-  for (int idx = tid; idx < bs * bs; idx += blockDim.x)
-    S[idx / bs][idx % bs] = Ab[(long long)(k0 + idx / bs) * N + k0 + idx % bs];
-  __syncthreads();
+  if (!PRE) {
+    for (int idx = tid; idx < bs * bs; idx += blockDim.x)
+      S[idx / bs][idx % bs] =
+          Ab[(long long)(k0 + idx / bs) * N + k0 + idx % bs];
+    __syncthreads();
+  }
   // TRSM staging buffer, declared up front: waves 1+ stage the FIRST chunk
   // of trailing panel rows into LDS concurrently with wave 0's serial
   // diagonal factor (the staging reads last step's SYRK output — global
@@ -287,10 +388,72 @@ __device__ __forceinline__ void chol_panel_body(
   // it; disjoint LDS regions).
   const int c0_first = k0 + CHOL_BS;
   const int rows_first = min(TPB, N - c0_first);
-  if (tid >= 64) {
-    for (int idx = tid - 64; idx < rows_first * CHOL_BS; idx += TPB - 64) {
+  if (PRE) {
+    // whole workgroup: coalesced stage of the previous panel's rows of the
+    // diagonal block into Lj (3 loads per thread) and of its solved rhs
+    // segment into Lj's extra row. This is all wave 0 waits for: the strip
+    // rows are staged wave-locally by waves 1+ (chol_strip_rows). Wave 0
+    // issues the loads of its own diagonal-block elements and rhs entry
+    // BEFORE the barrier, so their latency overlaps the staging.
+    const int kp = k0 - CHOL_BS;
+    const int lr = tid & 15, lk = (tid >> 4) & 3;
+    float adiag[4][4];
+    float yv = 0.0f;
+    if (tid < 64) {
+#pragma unroll
+      for (int sub = 0; sub < 4; ++sub) {
+        const int r16 = (sub >> 1) * 16, c16 = (sub & 1) * 16;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int i = r16 + lk * 4 + r, j = c16 + lr;
+          adiag[sub][r] = (i < bs && j < bs)
+                              ? Ab[(long long)(k0 + i) * N + k0 + j]
+                              : 0.0f;
+        }
+      }
+      if (rhs_b != nullptr && tid < bs) yv = rhs_b[k0 + tid];
+    }
+    for (int idx = tid; idx < CHOL_BS * CHOL_BS; idx += TPB) {
       const int r = idx / CHOL_BS, c = idx % CHOL_BS;
-      P[r][c] = Ab[(long long)(c0_first + r) * N + k0 + c];
+      Lj[r][c ^ ((r & 7) << 2)] =
+          (k0 + r < N) ? Ab[(long long)(k0 + r) * N + kp + c] : 0.0f;
+    }
+    if (rhs_b != nullptr && tid >= TPB - CHOL_BS)
+      Lj[CHOL_BS][tid - (TPB - CHOL_BS)] = rhs_b[kp + tid - (TPB - CHOL_BS)];
+    __syncthreads();
+    if (tid < 64) {
+      // wave 0: updated diagonal block straight into S (only its lower
+      // triangle is updated, as in the SYRK tiles, and only that is read),
+      // then the rhs segment's update; the factor below waits for this
+#pragma unroll
+      for (int sub = 0; sub < 4; ++sub) {
+        const int r16 = (sub >> 1) * 16, c16 = (sub & 1) * 16;
+        const int ra = r16 + lr, rb = c16 + lr;
+        const f32x4 acc = chol_subtile_acc(Lj[ra], (ra & 7) << 2, Lj[rb],
+                                           (rb & 7) << 2, lk);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int i = r16 + lk * 4 + r, j = c16 + lr;
+          if (i < bs && j < bs)
+            S[i][j] = (j <= i) ? adiag[sub][r] - acc[r] : adiag[sub][r];
+        }
+      }
+      if (rhs_b != nullptr && tid < bs)
+        rhs_b[k0 + tid] = chol_rhs_row_update(Lj[tid], (tid & 7) << 2,
+                                              Lj[CHOL_BS], yv);
+      __threadfence_block();  // S rows cross lanes inside wave 0
+    }
+  }
+  if (tid >= 64) {
+    if (PRE) {
+      // waves 1+: the first chunk's strip update, concurrent with wave 0
+      chol_strip_rows(Ab, N, k0, c0_first, rows_first, P, Lj, (tid >> 6) - 1,
+                      TPB / 64 - 1);
+    } else {
+      for (int idx = tid - 64; idx < rows_first * CHOL_BS; idx += TPB - 64) {
+        const int r = idx / CHOL_BS, c = idx % CHOL_BS;
+        P[r][c] = Ab[(long long)(c0_first + r) * N + k0 + c];
+      }
     }
   } else if (GROUP_COLS == 1) {
     // pure-shuffle factor (no LDS broadcast, no fences): per column j the
@@ -463,9 +626,14 @@ __device__ __forceinline__ void chol_panel_body(
   for (int c0 = c0_first; c0 < N; c0 += TPB) {
     const int rows = min(TPB, N - c0);
     if (c0 != c0_first) {
-      for (int idx = tid; idx < rows * CHOL_BS; idx += TPB) {
-        const int r = idx / CHOL_BS, c = idx % CHOL_BS;
-        P[r][c] = Ab[(long long)(c0 + r) * N + k0 + c];
+      if (PRE) {
+        // later chunks: every wave stages and updates its own row groups
+        chol_strip_rows(Ab, N, k0, c0, rows, P, Lj, tid >> 6, TPB / 64);
+      } else {
+        for (int idx = tid; idx < rows * CHOL_BS; idx += TPB) {
+          const int r = idx / CHOL_BS, c = idx % CHOL_BS;
+          P[r][c] = Ab[(long long)(c0 + r) * N + k0 + c];
+        }
       }
       __syncthreads();
     }
@@ -713,10 +881,12 @@ __global__ __launch_bounds__(CHOLP_TPB) void chol_syrk64_kernel(
 // Trailing update A[ti,tj] -= P_i P_j^T over 64x64 tiles of the submatrix
 // below/right of the panel; blockIdx.y enumerates lower-triangular tile
 // pairs, each 256-thread block computes a 4x4 register tile per thread.
+// r0 is the tile origin (first row and column the tiles cover): k0 + 32 for
+// the classic full trailing update, k0 + 64 for the look-ahead schedule's
+// role B, whose first 32 columns belong to role A's strip.
 __device__ __forceinline__ void chol_syrk_tile_body(
-    float* __restrict__ Ab, int N, int k0, int ti, int tj,
+    float* __restrict__ Ab, int N, int k0, int r0, int ti, int tj,
     float* __restrict__ rhs_b, float (*Pi)[CHOL_BS], float (*Pj)[CHOL_BS]) {
-  const int r0 = k0 + CHOL_BS;  // first trailing row
   const int i0 = r0 + ti * SYRK_TS, j0 = r0 + tj * SYRK_TS;
   const int tid = threadIdx.x;
 
@@ -730,7 +900,6 @@ __device__ __forceinline__ void chol_syrk_tile_body(
 
   // MFMA tile core: C -= Pi * Pj^T on the matrix units (operand map and
   // rationale in the original kernel comment below).
-  typedef __attribute__((ext_vector_type(4))) float f32x4;
   const int wave = tid >> 6, lane = tid & 63;
   const int lr = lane & 15, lk = lane >> 4;
 #pragma unroll
@@ -738,14 +907,10 @@ __device__ __forceinline__ void chol_syrk_tile_body(
     const int sub = wave * 4 + sIdx;        // 4x4 grid of 16x16 subtiles
     if (sub >= 16) break;  // blocks wider than 4 waves: extra waves idle
     const int r16 = (sub >> 2) * 16, c16 = (sub & 3) * 16;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < CHOL_BS; k += 4) {
-      const int ra = r16 + lr, rb = c16 + lr;
-      const float a = Pi[ra][(k + lk) ^ ((ra & 7) << 2)];  // A[i][k]
-      const float b = Pj[rb][(k + lk) ^ ((rb & 7) << 2)];  // B[k][j]=Pj[j][k]
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
-    }
+    const int ra = r16 + lr, rb = c16 + lr;
+    // A[i][k] = Pi[i][k], B[k][j] = Pj[j][k]
+    const f32x4 acc =
+        chol_subtile_acc(Pi[ra], (ra & 7) << 2, Pj[rb], (rb & 7) << 2, lk);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int i = i0 + r16 + lk * 4 + r;
@@ -758,12 +923,8 @@ __device__ __forceinline__ void chol_syrk_tile_body(
   if (rhs_b != nullptr && ti == tj && tid < 64) {
     const int i = i0 + tid;
     if (i < N) {
-      const float* z = rhs_b + k0;
-      float acc = rhs_b[i];
-#pragma unroll
-      for (int t = 0; t < CHOL_BS; ++t)
-        acc = fmaf(-Pi[tid][t ^ ((tid & 7) << 2)], z[t], acc);
-      rhs_b[i] = acc;
+      rhs_b[i] = chol_rhs_row_update(Pi[tid], (tid & 7) << 2, rhs_b + k0,
+                                     rhs_b[i]);
     }
   }
 }
@@ -798,8 +959,52 @@ __global__ __launch_bounds__(CHOLP_TPB) void chol_syrk_kernel(
     tj = p + off;
     ti += off;
   }
-  chol_syrk_tile_body(Ab, N, k0, ti, tj,
+  chol_syrk_tile_body(Ab, N, k0, k0 + CHOL_BS, ti, tj,
                       rhs ? rhs + (long long)b * N : nullptr, Pi, Pj);
+}
+
+// ------------------------------------------------------ look-ahead step
+// One launch per panel step s >= 1 (k0 = 32 s), grid (B, 1 + tiles); the
+// kernel boundary is the only synchronization (one stream, no events, no
+// flags). Both roles consume panel s-1, written by the previous launch:
+//   block y = 0  (role A): applies panel s-1's update to strip s only
+//     (rows >= k0, columns k0..k0+31) and to the rhs segment, then factors
+//     and solves panel s exactly like chol_panel_kernel;
+//   blocks y >= 1 (role B): apply panel s-1's update to the REST of the
+//     trailing matrix (rows and columns >= k0 + 32, rhs rows >= k0 + 32) as
+//     64x64 tiles with origin k0 + 32.
+// Written regions are disjoint (A: columns [k0, k0+32) and rhs [k0, k0+32);
+// B: columns and rhs rows >= k0+32), and neither role reads what the other
+// writes: both read only columns [k0-32, k0) and rhs [k0-32, k0). The
+// full-matrix SYRK therefore runs BESIDE the panel instead of in front of
+// it: ceil(N/32) launches instead of 2 ceil(N/32) - 1. Element values are
+// those of the classic schedule bit for bit (shared inlines above).
+// Role B's tile buffers alias the panel's TRSM buffer P (a block has one
+// role), keeping the static LDS at the panel's ~55 KB + 4 KB for Lj.
+template <int GROUP_COLS, int TPB>
+__global__ __launch_bounds__(TPB) void chol_step_kernel(
+    float* __restrict__ A, float* __restrict__ logdet, int* __restrict__ info,
+    int N, int k0, float* __restrict__ rhs) {
+  __shared__ float S[CHOL_BS][CHOL_BS + 1];
+  __shared__ float colbuf4[GROUP_COLS][CHOL_BS];
+  __shared__ float P[TPB][CHOL_BS + 1];
+  __shared__ float Lj[CHOL_BS + 1][CHOL_BS];  // + the solved rhs segment
+  static_assert(TPB * (CHOL_BS + 1) >= 2 * SYRK_TS * CHOL_BS,
+                "tile buffers must fit in the TRSM buffer");
+  const int b = blockIdx.x;
+  float* Ab = A + (long long)b * N * N;
+  float* rhs_b = rhs ? rhs + (long long)b * N : nullptr;
+  if (blockIdx.y == 0) {
+    chol_panel_body<GROUP_COLS, TPB, true>(Ab, logdet + b, info + b, N, k0,
+                                           rhs_b, S, colbuf4, P, Lj);
+  } else {
+    float(*Pi)[CHOL_BS] = (float(*)[CHOL_BS]) & P[0][0];
+    float(*Pj)[CHOL_BS] = Pi + SYRK_TS;
+    int p = blockIdx.y - 1, ti = 0;
+    while (p > ti) { p -= ti + 1; ++ti; }
+    chol_syrk_tile_body(Ab, N, k0 - CHOL_BS, k0 + CHOL_BS, ti, p, rhs_b, Pi,
+                        Pj);
+  }
 }
 
 // Blocked forward substitution: solve L z = y for R right-hand sides.
@@ -995,6 +1200,93 @@ static inline int panel_tpb() {
 }
 #define LAUNCH_PANEL(B_, stream_, A_, logdet_, info_, N_, k0_, rhs_)                 do {                                                                           const int tpb_ = panel_tpb();                                                if (panel_group_cols() == 1) {                                                 if (tpb_ == 384)                                                               hipLaunchKernelGGL((chol_panel_kernel<1, 384>), dim3(B_), dim3(384),                            0, stream_, A_, logdet_, info_, N_, k0_, rhs_);             else                                                                           hipLaunchKernelGGL((chol_panel_kernel<1, 256>), dim3(B_), dim3(256),                            0, stream_, A_, logdet_, info_, N_, k0_, rhs_);           } else if (panel_group_cols() == 2) {                                                 if (tpb_ == 384)                                                               hipLaunchKernelGGL((chol_panel_kernel<2, 384>), dim3(B_), dim3(384),                            0, stream_, A_, logdet_, info_, N_, k0_, rhs_);             else                                                                           hipLaunchKernelGGL((chol_panel_kernel<2, 256>), dim3(B_), dim3(256),                            0, stream_, A_, logdet_, info_, N_, k0_, rhs_);           } else {                                                                       if (tpb_ == 384)                                                               hipLaunchKernelGGL((chol_panel_kernel<4, 384>), dim3(B_), dim3(384),                            0, stream_, A_, logdet_, info_, N_, k0_, rhs_);             else                                                                           hipLaunchKernelGGL((chol_panel_kernel<4, 256>), dim3(B_), dim3(256),                            0, stream_, A_, logdet_, info_, N_, k0_, rhs_);           }                                                                          } while (0)
 
+template <int GROUP_COLS, int TPB>
+static inline void launch_chol_step_gt(dim3 grid, hipStream_t stream, float* A,
+                                       float* logdet, int* info, int N, int k0,
+                                       float* rhs) {
+  hipLaunchKernelGGL((chol_step_kernel<GROUP_COLS, TPB>), grid, dim3(TPB), 0,
+                     stream, A, logdet, info, N, k0, rhs);
+}
+
+// look-ahead step launch under the same group / width switches as the panel
+static inline void launch_chol_step(int B, int tiles, hipStream_t stream,
+                                    float* A, float* logdet, int* info, int N,
+                                    int k0, float* rhs) {
+  const dim3 grid(B, 1 + tiles);
+  const bool wide = panel_tpb() == 384;
+  switch (panel_group_cols()) {
+    case 1:
+      if (wide) launch_chol_step_gt<1, 384>(grid, stream, A, logdet, info, N, k0, rhs);
+      else launch_chol_step_gt<1, 256>(grid, stream, A, logdet, info, N, k0, rhs);
+      break;
+    case 2:
+      if (wide) launch_chol_step_gt<2, 384>(grid, stream, A, logdet, info, N, k0, rhs);
+      else launch_chol_step_gt<2, 256>(grid, stream, A, logdet, info, N, k0, rhs);
+      break;
+    default:
+      if (wide) launch_chol_step_gt<4, 384>(grid, stream, A, logdet, info, N, k0, rhs);
+      else launch_chol_step_gt<4, 256>(grid, stream, A, logdet, info, N, k0, rhs);
+  }
+}
+
+// trailing-update schedule of the 32-wide multik path:
+//   classic    — panel launch, then a full-matrix SYRK launch, per step;
+//   look-ahead — plain panel 0, then ONE chol_step_kernel launch per
+//                remaining panel (bitwise-identical results).
+// DMOSOPT_CHOL_LOOKAHEAD=1/0 selects it, latched once per process;
+// measured A/B in profiles/README.md.
+enum { CHOL_SCHED_CLASSIC = 0, CHOL_SCHED_LOOKAHEAD = 1 };
+#define CHOL_LOOKAHEAD_DEFAULT 1
+static inline int chol_lookahead_default() {
+  static int la = -1;
+  if (la < 0) {
+    const char* e = getenv("DMOSOPT_CHOL_LOOKAHEAD");
+    la = e ? (e[0] == '1' ? 1 : 0) : CHOL_LOOKAHEAD_DEFAULT;
+  }
+  return la;
+}
+
+static void chol_multik_classic(float* A, float* logdet, int* info,
+                                float* rhs, int B, int N, hipStream_t stream) {
+  for (int k0 = 0; k0 < N; k0 += CHOL_BS) {
+    LAUNCH_PANEL(B, stream, A, logdet, info, N, k0, rhs);
+    const int trailing = N - k0 - CHOL_BS;
+    if (trailing > 0) {
+      const int nt = (trailing + SYRK_TS - 1) / SYRK_TS;
+      hipLaunchKernelGGL(chol_syrk_kernel, dim3(B, nt * (nt + 1) / 2),
+                         dim3(CHOLP_TPB), 0, stream, A, N, k0, nt, -1, 0,
+                         rhs);
+    }
+  }
+}
+
+static void chol_multik_lookahead(float* A, float* logdet, int* info,
+                                  float* rhs, int B, int N,
+                                  hipStream_t stream) {
+  LAUNCH_PANEL(B, stream, A, logdet, info, N, 0, rhs);
+  for (int k0 = CHOL_BS; k0 < N; k0 += CHOL_BS) {
+    // role B covers rows/columns >= k0 + 32; none left on the last steps
+    const int trailing = N - k0 - CHOL_BS;
+    const int nt = trailing > 0 ? (trailing + SYRK_TS - 1) / SYRK_TS : 0;
+    launch_chol_step(B, nt * (nt + 1) / 2, stream, A, logdet, info, N, k0,
+                     rhs);
+  }
+}
+
+// Explicit-schedule entry (tests and isolated timing compare the two
+// schedules inside one process; the env switches are latched).
+extern "C" void launch_cholesky_multik_sched(float* A, float* logdet,
+                                             int* info, float* rhs, int B,
+                                             int N, int sched,
+                                             hipStream_t stream) {
+  hipLaunchKernelGGL(zero_f32_kernel, dim3((B + 255) / 256), dim3(256), 0,
+                     stream, logdet, B);
+  if (sched == CHOL_SCHED_LOOKAHEAD)
+    chol_multik_lookahead(A, logdet, info, rhs, B, N, stream);
+  else
+    chol_multik_classic(A, logdet, info, rhs, B, N, stream);
+}
+
 extern "C" void launch_cholesky_multik(float* A, float* logdet, int* info,
                                        float* rhs, int B, int N,
                                        hipStream_t stream) {
@@ -1052,16 +1344,10 @@ extern "C" void launch_cholesky_multik(float* A, float* logdet, int* info,
     return;
   }
   if (!overlap) {
-    for (int k0 = 0; k0 < N; k0 += CHOL_BS) {
-      LAUNCH_PANEL(B, stream, A, logdet, info, N, k0, rhs);
-      const int trailing = N - k0 - CHOL_BS;
-      if (trailing > 0) {
-        const int nt = (trailing + SYRK_TS - 1) / SYRK_TS;
-        hipLaunchKernelGGL(chol_syrk_kernel, dim3(B, nt * (nt + 1) / 2),
-                           dim3(CHOLP_TPB), 0, stream, A, N, k0, nt, -1, 0,
-                           rhs);
-      }
-    }
+    if (chol_lookahead_default())
+      chol_multik_lookahead(A, logdet, info, rhs, B, N, stream);
+    else
+      chol_multik_classic(A, logdet, info, rhs, B, N, stream);
     return;
   }
   int kstep = 0;
@@ -1188,7 +1474,7 @@ __global__ __launch_bounds__(PERSIST_TPB) void chol_persist_kernel(
       int p = t, ti = 0;
       while (p > ti) { p -= ti + 1; ++ti; }
       const int tj = p;
-      chol_syrk_tile_body(Ab, N, k0, ti, tj, rhs_b, Pi, Pj);
+      chol_syrk_tile_body(Ab, N, k0, k0 + CHOL_BS, ti, tj, rhs_b, Pi, Pj);
       __threadfence();  // release tile writes
       __syncthreads();
       if (tid == 0) atomicAdd(tiles_done, 1);
