@@ -209,10 +209,7 @@ _nmll_graphs: dict = {}
 def _nmll_graph_enabled() -> bool:
     import os
 
-    return (
-        os.environ.get("DMOSOPT_NMLL_GRAPH", "1") == "1"
-        and os.environ.get("DMOSOPT_CHOL_OVERLAP", "0") != "1"  # multi-stream
-    )
+    return os.environ.get("DMOSOPT_NMLL_GRAPH", "1") == "1"
 
 
 def _nmll_bind_enabled() -> bool:

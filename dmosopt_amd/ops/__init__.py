@@ -356,9 +356,9 @@ def chol_factor_multik(K, rhs=None, schedule="classic"):
     carried through the fused forward solve.
 
     Returns (L, logdet (B,), info (B,), z) with z = L^-1 rhs (None without
-    rhs); the inputs are left untouched. The DMOSOPT_CHOL_* switches are
-    latched once per process, so this is how the two schedules are compared
-    inside one process. Native only: a missing extension is an error."""
+    rhs); the inputs are left untouched. DMOSOPT_CHOL_LOOKAHEAD is latched
+    once per process, so this is how the two schedules are compared inside
+    one process. Native only: a missing extension is an error."""
     if not (_use_native(K) and K.dtype == torch.float32):
         raise RuntimeError("chol_factor_multik needs the native extension "
                            "and a float32 GPU tensor")

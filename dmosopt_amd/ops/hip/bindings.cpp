@@ -19,8 +19,8 @@ void launch_matern_assemble(const float*, const float*, const float*, float*,
 void launch_cholesky_batched(float*, float*, int*, int, int, hipStream_t);
 void launch_cholesky_multik_sched(float*, float*, int*, float*, int, int, int,
                                   hipStream_t);
-int launch_cholesky_fused_solve(float*, float*, int*, float*, int*, int,
-                                int, hipStream_t);
+int launch_cholesky_fused_solve(float*, float*, int*, float*, int, int,
+                                hipStream_t);
 void launch_forward_solve_batched(const float*, float*, int, int, int,
                                   hipStream_t);
 void launch_backward_solve_batched(const float*, float*, int, int, int,
@@ -156,12 +156,10 @@ torch::Tensor gp_nmll(torch::Tensor X, torch::Tensor theta, torch::Tensor y,
   // fused factor+solve: the rhs rides the multik launch chain (panel solves
   // its 32-entry segment, the SYRK's diagonal tiles apply the trailing
   // update) — no separate ~61 us serial TRSV kernel per NMLL
-  auto ws = torch::empty({2 * B}, X.options().dtype(torch::kInt32));
   if (launch_cholesky_fused_solve(K.data_ptr<float>(),
                                   logdet.data_ptr<float>(),
                                   info.data_ptr<int>(), Z.data_ptr<float>(),
-                                  ws.data_ptr<int>(), B, N,
-                                  cur_stream()) != 0) {
+                                  B, N, cur_stream()) != 0) {
     launch_cholesky_batched(K.data_ptr<float>(), logdet.data_ptr<float>(),
                             info.data_ptr<int>(), B, N, cur_stream());
     launch_forward_solve_batched(K.data_ptr<float>(), Z.data_ptr<float>(), B,
@@ -372,9 +370,9 @@ std::vector<torch::Tensor> cholesky_batched_(torch::Tensor A) {
 
 // Multi-launch factorization with an EXPLICIT trailing-update schedule
 // (0 = classic panel + SYRK launches, 1 = look-ahead step launches) and an
-// optional rhs (B, N) carried through the fused forward solve. The env
-// switches are latched per process, so this is the only way to compare the
-// two schedules inside one process. In place: A -> L, rhs -> L^-1 rhs.
+// optional rhs (B, N) carried through the fused forward solve.
+// DMOSOPT_CHOL_LOOKAHEAD is latched per process, so this is the only way to
+// compare the two schedules inside one process. In place: A -> L, rhs -> L^-1 rhs.
 std::vector<torch::Tensor> cholesky_multik_sched_(
     torch::Tensor A, c10::optional<torch::Tensor> rhs, int64_t sched) {
   CHECK_GPU(A);

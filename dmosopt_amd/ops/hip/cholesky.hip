@@ -1,22 +1,26 @@
 // Batched in-place Cholesky factorization, log-determinant, and
 // forward/backward substitution — the GP fit/predict linear algebra
 // (replaces the LAPACK calls inside sklearn GaussianProcessRegressor,
-// reference model.py:1246-1265).
+// reference model.py:1246-1265). Exact fp32; non-PD pivots clamp and set
+// info[b]. Two right-looking blocked factorizations (BS = 32), chosen by
+// batch count in launch_cholesky_batched:
 //
-// Design: ONE workgroup (256 threads) per matrix, right-looking blocked
-// factorization (BS = 32). v2 data path (gfx950):
+// B > CHOL_MULTIK_MAX_B: cholesky_batched_kernel, ONE workgroup (1024
+// threads) per matrix, batch parallelism fills the chip:
 //   * diagonal block factored in LDS (stride-33 rows: conflict-free),
 //   * panel solve with each ROW held in 32 VGPRs (float4 global loads),
 //     back-substituted against the LDS diagonal block,
 //   * trailing SYRK update C -= P P^T fed ENTIRELY from LDS: the panel is
 //     staged in chunk pairs (CHUNK x 32 floats each) so every multiply
 //     reads LDS, with 2x2 register tiles per thread.
-// Sized for the MO-ASMO regime: B = objectives x SCE-UA complexes matrices
-// of N <= ~4k factorized concurrently, one CU each; batch parallelism fills
-// the chip. Exact fp32; non-PD pivots clamp and set info[b].
+//
+// B <= CHOL_MULTIK_MAX_B: the multi-launch path further down (a 384-thread
+// panel block per matrix plus 256-thread MFMA SYRK tiles spread over the
+// chip), optionally carrying a fused forward solve.
 
 #include "common.h"
 #include <math.h>
+#include <stdlib.h>
 
 #define CHOL_BS 32
 #ifndef CHOL_TPB
@@ -35,7 +39,6 @@ struct CholLds {
 
 // ~100 KiB of LDS: above the 64 KiB static default, so allocated
 // dynamically (gfx950 has 160 KiB per CU).
-template <bool WAVE_DIAG>
 __global__ __launch_bounds__(CHOL_TPB) void cholesky_batched_kernel(
     float* __restrict__ A,       // (B, N, N)
     float* __restrict__ logdet,  // (B,)
@@ -52,92 +55,36 @@ __global__ __launch_bounds__(CHOL_TPB) void cholesky_batched_kernel(
   for (int k0 = 0; k0 < N; k0 += CHOL_BS) {
     const int bs = min(CHOL_BS, N - k0);
 
-    // --- factor the diagonal block WAVE-SYNCHRONOUSLY in wave 0: lane l
-    // holds row l in registers; column values broadcast with shuffles —
-    // zero barriers inside the 32-step j loop (the previous LDS version
-    // paid ~100 workgroup barriers per k-step).
-    if (WAVE_DIAG && tid < WAVE_SIZE) {
-      const int lane = tid;
-      // the j/c loops are FULLY unrolled (compile-time indices) so r[]
-      // stays in registers — runtime-indexed register arrays spill
-      float r[CHOL_BS];
-#pragma unroll
-      for (int c = 0; c < CHOL_BS; ++c)
-        r[c] = (lane < bs && c < bs) ? M[(long long)(k0 + lane) * N + k0 + c]
-                                     : 0.f;
-      float ld_part = 0.f;
-      int bad = 0;
-#pragma unroll
-      for (int j = 0; j < CHOL_BS; ++j) {
-        if (j >= bs) break;
-        // lane j holds the fully-updated pivot
-        float piv = __shfl(r[j], j);
-        if (piv <= 0.f) {
-          bad = 1;
-          piv = 1e-30f;
+    // --- diagonal block: staged into LDS and factored there column by
+    // column with workgroup barriers
+    for (int idx = tid; idx < bs * bs; idx += CHOL_TPB)
+      L.S[idx / bs][idx % bs] =
+          M[(long long)(k0 + idx / bs) * N + k0 + idx % bs];
+    __syncthreads();
+    for (int j = 0; j < bs; ++j) {
+      if (tid == 0) {
+        float djj = L.S[j][j];
+        if (djj <= 0.f) {
+          info[b] = 1;
+          djj = 1e-30f;
         }
-        const float sjj = sqrtf(piv);
-        if (lane == j) {
-          r[j] = sjj;
-          ld_part += __logf(sjj);
-        }
-        const float lij = (lane > j && lane < bs) ? r[j] / sjj : 0.f;
-        if (lane > j && lane < bs) r[j] = lij;
-        // rank-1 update: a[i][c] -= L[i][j] * L[c][j] (lower triangle)
-#pragma unroll
-        for (int c = j + 1; c < CHOL_BS; ++c) {
-          if (c >= bs) break;
-          const float lcj = __shfl(lij, c);
-          if (lane >= c && lane < bs) r[c] = fmaf(-lij, lcj, r[c]);
-        }
+        L.S[j][j] = sqrtf(djj);
+        L.ld_accum += __logf(L.S[j][j]);
       }
-      if (lane < bs) {
-#pragma unroll
-        for (int c = 0; c < CHOL_BS; ++c) {
-          const float v = (c <= lane) ? r[c] : 0.f;
-          if (c < bs) {
-            L.S[lane][c] = v;
-            M[(long long)(k0 + lane) * N + k0 + c] = v;
-          }
-        }
-      }
-      const float ld_sum = warp_reduce_sum(ld_part);
-      if (lane == 0) {
-        L.ld_accum += ld_sum;
-        if (bad) info[b] = 1;  // bad is wave-uniform (piv is broadcast)
-      }
-    }
-    if (!WAVE_DIAG) {
-      // LDS/barrier variant of the diagonal-block factorization
-      for (int idx = tid; idx < bs * bs; idx += CHOL_TPB)
-        L.S[idx / bs][idx % bs] =
-            M[(long long)(k0 + idx / bs) * N + k0 + idx % bs];
       __syncthreads();
-      for (int j = 0; j < bs; ++j) {
-        if (tid == 0) {
-          float djj = L.S[j][j];
-          if (djj <= 0.f) {
-            info[b] = 1;
-            djj = 1e-30f;
-          }
-          L.S[j][j] = sqrtf(djj);
-          L.ld_accum += __logf(L.S[j][j]);
-        }
-        __syncthreads();
-        for (int i = j + 1 + tid; i < bs; i += CHOL_TPB) L.S[i][j] /= L.S[j][j];
-        __syncthreads();
-        const int rem_d = bs - j - 1;
-        for (int idx = tid; idx < rem_d * rem_d; idx += CHOL_TPB) {
-          const int rr = j + 1 + idx / rem_d;
-          const int cc = j + 1 + idx % rem_d;
-          if (cc <= rr) L.S[rr][cc] -= L.S[rr][j] * L.S[cc][j];
-        }
-        __syncthreads();
+      for (int i = j + 1 + tid; i < bs; i += CHOL_TPB) L.S[i][j] /= L.S[j][j];
+      __syncthreads();
+      const int rem_d = bs - j - 1;
+      for (int idx = tid; idx < rem_d * rem_d; idx += CHOL_TPB) {
+        const int rr = j + 1 + idx / rem_d;
+        const int cc = j + 1 + idx % rem_d;
+        if (cc <= rr) L.S[rr][cc] -= L.S[rr][j] * L.S[cc][j];
       }
-      for (int idx = tid; idx < bs * bs; idx += CHOL_TPB) {
-        const int rr = idx / bs, cc = idx % bs;
-        M[(long long)(k0 + rr) * N + k0 + cc] = (cc <= rr) ? L.S[rr][cc] : 0.f;
-      }
+      __syncthreads();
+    }
+    for (int idx = tid; idx < bs * bs; idx += CHOL_TPB) {
+      const int rr = idx / bs, cc = idx % bs;
+      M[(long long)(k0 + rr) * N + k0 + cc] = (cc <= rr) ? L.S[rr][cc] : 0.f;
     }
     __syncthreads();
 
@@ -238,17 +185,26 @@ __global__ __launch_bounds__(CHOL_TPB) void cholesky_batched_kernel(
 //
 // The single-block kernel above runs one block per matrix: at the headline
 // shape (B ~ 12 systems of N=300 from the speculative SCE-UA stages) that
-// leaves 244 of 256 CUs idle. Here each 32-column step is two stream-ordered
-// launches — a panel kernel (grid B) and a trailing-update SYRK kernel
-// (grid B x tile-pairs, 64x64 tiles) — so the SYRK, which is ~90% of the
-// FLOPs, spreads across B * O((N/64)^2) workgroups.
+// leaves 244 of 256 CUs idle. Here the trailing update, which is ~90% of the
+// FLOPs, runs as 64x64 tiles spread across B * O((N/64)^2) workgroups. Two
+// schedules with bit-identical results (chol_multik_classic /
+// chol_multik_lookahead below): a panel launch (grid B) followed by a SYRK
+// launch (grid B x tile-pairs) per 32-column step, or one combined
+// chol_step_kernel launch per step.
 
-#define CHOLP_TPB 256
-#define SYRK_TS 64  // trailing-update tile edge
+// Panel / step workgroup width: 384 threads solve the whole N=300 trailing
+// panel in ONE LDS chunk (256 needs two sequential chunk rounds: stage +
+// solve + writeback + 3 barriers each); static LDS caps the width at 384
+// (P[384][33] + S + colbuf = 55 KB < 64 KB).
+#define CHOL_PANEL_TPB 384
+// Columns factored per round of the diagonal factor (chol_panel_body).
+#define CHOL_GROUP_COLS 2
+#define CHOL_SYRK_TPB 256  // SYRK tile workgroup: 4 waves x 4 sub-tiles
+#define SYRK_TS 64         // trailing-update tile edge
 
 // Shared arithmetic of the rank-32 trailing update. EVERY path that applies
-// a panel's update — the SYRK tile kernel, the persistent kernel's tiles and
-// both roles of the look-ahead step kernel — goes through these two inlines,
+// a panel's update — the SYRK tile kernel and both roles of the look-ahead
+// step kernel — goes through these two inlines,
 // so an output element's value cannot depend on which block, tile origin or
 // schedule computed it (NOTES.md -ffp-contract rule: one inline per chain).
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -338,9 +294,8 @@ __device__ __forceinline__ void chol_strip_rows(
 // Factor the 32x32 diagonal block at (k0,k0) and panel-solve the rows below
 // it. One block per matrix; also accumulates the step's logdet contribution
 // deterministically (no atomics: k-steps are stream-ordered).
-// Device body shared by the per-step panel kernel and the persistent
-// whole-factorization kernel (chol_persist_kernel): identical arithmetic,
-// only the launch wrapper differs.
+// Device body of chol_panel_kernel (PRE = false) and of chol_step_kernel's
+// role A (PRE = true), run by CHOL_PANEL_TPB threads.
 //
 // PRE = true is the look-ahead schedule's role A (chol_step_kernel): the
 // previous panel's rank-32 update has been applied everywhere EXCEPT this
@@ -350,11 +305,11 @@ __device__ __forceinline__ void chol_strip_rows(
 // then proceeds exactly as the plain panel. Lj ([33][32]) stages the
 // previous panel's rows k0..k0+31 (swizzled) and, in row 32, its solved rhs
 // segment; unused (nullptr) when PRE is false.
-template <int GROUP_COLS, int TPB, bool PRE = false>
+template <bool PRE>
 __device__ __forceinline__ void chol_panel_body(
     float* __restrict__ Ab, float* __restrict__ logdet_b,
     int* __restrict__ info_b, int N, int k0, float* __restrict__ rhs_b,
-    float (*S)[CHOL_BS + 1], float (*colbuf4)[CHOL_BS],
+    float (*S)[CHOL_BS + 1], float (*colbuf)[CHOL_BS],
     float (*P)[CHOL_BS + 1], float (*Lj)[CHOL_BS] = nullptr) {
   // rhs != nullptr: FUSED FORWARD SOLVE (bordered-matrix scheme). rhs (B, N)
   // starts as y and finishes as z = L^-1 y without a separate TRSV kernel:
@@ -387,7 +342,7 @@ __device__ __forceinline__ void chol_panel_body(
   // entirely under the factor's shuffle chain instead of serializing after
   // it; disjoint LDS regions).
   const int c0_first = k0 + CHOL_BS;
-  const int rows_first = min(TPB, N - c0_first);
+  const int rows_first = min(CHOL_PANEL_TPB, N - c0_first);
   if (PRE) {
     // whole workgroup: coalesced stage of the previous panel's rows of the
     // diagonal block into Lj (3 loads per thread) and of its solved rhs
@@ -413,13 +368,14 @@ __device__ __forceinline__ void chol_panel_body(
       }
       if (rhs_b != nullptr && tid < bs) yv = rhs_b[k0 + tid];
     }
-    for (int idx = tid; idx < CHOL_BS * CHOL_BS; idx += TPB) {
+    for (int idx = tid; idx < CHOL_BS * CHOL_BS; idx += CHOL_PANEL_TPB) {
       const int r = idx / CHOL_BS, c = idx % CHOL_BS;
       Lj[r][c ^ ((r & 7) << 2)] =
           (k0 + r < N) ? Ab[(long long)(k0 + r) * N + kp + c] : 0.0f;
     }
-    if (rhs_b != nullptr && tid >= TPB - CHOL_BS)
-      Lj[CHOL_BS][tid - (TPB - CHOL_BS)] = rhs_b[kp + tid - (TPB - CHOL_BS)];
+    if (rhs_b != nullptr && tid >= CHOL_PANEL_TPB - CHOL_BS)
+      Lj[CHOL_BS][tid - (CHOL_PANEL_TPB - CHOL_BS)] =
+          rhs_b[kp + tid - (CHOL_PANEL_TPB - CHOL_BS)];
     __syncthreads();
     if (tid < 64) {
       // wave 0: updated diagonal block straight into S (only its lower
@@ -448,65 +404,13 @@ __device__ __forceinline__ void chol_panel_body(
     if (PRE) {
       // waves 1+: the first chunk's strip update, concurrent with wave 0
       chol_strip_rows(Ab, N, k0, c0_first, rows_first, P, Lj, (tid >> 6) - 1,
-                      TPB / 64 - 1);
+                      CHOL_PANEL_TPB / 64 - 1);
     } else {
-      for (int idx = tid - 64; idx < rows_first * CHOL_BS; idx += TPB - 64) {
+      for (int idx = tid - 64; idx < rows_first * CHOL_BS;
+           idx += CHOL_PANEL_TPB - 64) {
         const int r = idx / CHOL_BS, c = idx % CHOL_BS;
         P[r][c] = Ab[(long long)(c0_first + r) * N + k0 + c];
       }
-    }
-  } else if (GROUP_COLS == 1) {
-    // pure-shuffle factor (no LDS broadcast, no fences): per column j the
-    // rank-1 update's multiplier L[c][j] moves by one __shfl per target
-    // column — 31 independent shuffles that pipeline freely, where the
-    // LDS-broadcast rounds serialize on two __threadfence_block each.
-    // fmaf order per element is ascending-j rank-1, identical to the
-    // grouped variant: the factor is bitwise unchanged.
-    const int lane = tid;
-    float r[CHOL_BS];
-#pragma unroll
-    for (int t = 0; t < CHOL_BS; ++t)
-      r[t] = (lane < bs && t < bs) ? S[lane][t] : 0.0f;
-    float mylog = 0.0f;
-    int bad = 0;
-#pragma unroll
-    for (int j = 0; j < CHOL_BS; ++j) {
-      if (j >= bs) break;
-      float d = __shfl(r[j], j);
-      if (d <= 0.0f || !isfinite(d)) {
-        bad = bad ? bad : (k0 + j + 1);
-        d = 1e-30f;
-      }
-      d = sqrtf(d);
-      if (lane == j) {
-        r[j] = d;
-        mylog += logf(d);
-      } else if (lane > j) {
-        r[j] /= d;
-      }
-      const float lij = r[j];
-#pragma unroll
-      for (int c = j + 1; c < CHOL_BS; ++c) {
-        if (c >= bs) break;
-        const float lcj = __shfl(lij, c);
-        if (lane >= c) r[c] = fmaf(-lij, lcj, r[c]);
-      }
-    }
-    if (lane < bs) {
-#pragma unroll
-      for (int t = 0; t < CHOL_BS; ++t) {
-        if (t >= bs) continue;
-        S[lane][t] = r[t];
-      }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-      mylog += __shfl_down(mylog, off);
-      const int ob = __shfl_down(bad, off);
-      bad = bad ? bad : ob;
-    }
-    if (lane == 0) {
-      *logdet_b += mylog;
-      if (bad && *info_b == 0) *info_b = bad;
     }
   } else {
     const int lane = tid;
@@ -516,28 +420,29 @@ __device__ __forceinline__ void chol_panel_body(
       r[t] = (lane < bs && t < bs) ? S[lane][t] : 0.0f;
     float mylog = 0.0f;
     int bad = 0;
-    // GROUP_COLS columns per round: within the group each column first
+    // CHOL_GROUP_COLS columns per round: within the group each column first
     // receives the updates of its in-group predecessors, is factored
     // (shfl pivot + sqrt + div), and broadcast through LDS with ONE
     // workgroup fence; then ONE fused rank-GROUP pass updates the
-    // remaining columns. Quarters the update-loop rounds on the serial
+    // remaining columns. Halves the update-loop rounds on the serial
     // pivot chain (the dominant latency of this kernel) while keeping the
-    // fmaf sequence PER ELEMENT identical to the one-column version —
-    // the factor is bitwise unchanged (SCE-UA accept decisions are
-    // bit-stable). Measured A/B in profiles/README.md.
+    // fmaf sequence PER ELEMENT that of sequential rank-1 passes — the
+    // factor does not depend on the group size (SCE-UA accept decisions
+    // are bit-stable). Groups of 4 and a pure-shuffle factor measured
+    // slower: profiles/README.md.
 #pragma unroll
-    for (int g = 0; g < CHOL_BS; g += GROUP_COLS) {
+    for (int g = 0; g < CHOL_BS; g += CHOL_GROUP_COLS) {
       if (g >= bs) continue;
 #pragma unroll
-      for (int q = 0; q < GROUP_COLS; ++q) {
+      for (int q = 0; q < CHOL_GROUP_COLS; ++q) {
         const int j = g + q;
         if (j >= bs) break;
         // in-group predecessor updates for column j (same order as the
         // sequential rank-1 passes)
 #pragma unroll
-        for (int p = 0; p < GROUP_COLS; ++p) {
+        for (int p = 0; p < CHOL_GROUP_COLS; ++p) {
           if (p >= q) break;
-          if (lane >= j) r[j] = fmaf(-r[g + p], colbuf4[p][j], r[j]);
+          if (lane >= j) r[j] = fmaf(-r[g + p], colbuf[p][j], r[j]);
         }
         float d = __shfl(r[j], j);
         if (d <= 0.0f || !isfinite(d)) {
@@ -554,19 +459,19 @@ __device__ __forceinline__ void chol_panel_body(
         // broadcast column j through LDS with ONE workgroup fence: the
         // reads then pipeline freely, unlike a per-t __shfl chain
         // (ds_bpermute each) or a volatile pointer (per-access ordering)
-        if (lane < bs) colbuf4[q][lane] = r[j];
+        if (lane < bs) colbuf[q][lane] = r[j];
         __threadfence_block();
       }
       // fused rank-GROUP update of the columns beyond the group
-      const int gend = min(g + GROUP_COLS, bs);
+      const int gend = min(g + CHOL_GROUP_COLS, bs);
 #pragma unroll
       for (int t = 0; t < CHOL_BS; ++t) {
-        if (t < g + GROUP_COLS || t >= bs) continue;
+        if (t < g + CHOL_GROUP_COLS || t >= bs) continue;
         if (lane >= t) {
 #pragma unroll
-          for (int q = 0; q < GROUP_COLS; ++q) {
+          for (int q = 0; q < CHOL_GROUP_COLS; ++q) {
             if (g + q >= gend) break;
-            r[t] = fmaf(-r[g + q], colbuf4[q][t], r[t]);
+            r[t] = fmaf(-r[g + q], colbuf[q][t], r[t]);
           }
         }
       }
@@ -609,7 +514,8 @@ __device__ __forceinline__ void chol_panel_body(
   }
   // factored-block writeback by waves 1+ (concurrent with wave 0's rhs
   // solve above; both only READ S)
-  for (int idx = tid - 64; idx >= 0 && idx < bs * bs; idx += TPB - 64) {
+  for (int idx = tid - 64; idx >= 0 && idx < bs * bs;
+       idx += CHOL_PANEL_TPB - 64) {
     const int i = idx / bs, t = idx % bs;
     if (t <= i) Ab[(long long)(k0 + i) * N + k0 + t] = S[i][t];
   }
@@ -623,14 +529,15 @@ __device__ __forceinline__ void chol_panel_body(
   // written back coalesced. The FIRST chunk was pre-staged during the
   // factor. Trailing rows exist only under a FULL panel
   // (k0 + bs < N implies bs == CHOL_BS): constant trip counts throughout.
-  for (int c0 = c0_first; c0 < N; c0 += TPB) {
-    const int rows = min(TPB, N - c0);
+  for (int c0 = c0_first; c0 < N; c0 += CHOL_PANEL_TPB) {
+    const int rows = min(CHOL_PANEL_TPB, N - c0);
     if (c0 != c0_first) {
       if (PRE) {
         // later chunks: every wave stages and updates its own row groups
-        chol_strip_rows(Ab, N, k0, c0, rows, P, Lj, tid >> 6, TPB / 64);
+        chol_strip_rows(Ab, N, k0, c0, rows, P, Lj, tid >> 6,
+                        CHOL_PANEL_TPB / 64);
       } else {
-        for (int idx = tid; idx < rows * CHOL_BS; idx += TPB) {
+        for (int idx = tid; idx < rows * CHOL_BS; idx += CHOL_PANEL_TPB) {
           const int r = idx / CHOL_BS, c = idx % CHOL_BS;
           P[r][c] = Ab[(long long)(c0 + r) * N + k0 + c];
         }
@@ -656,7 +563,7 @@ __device__ __forceinline__ void chol_panel_body(
       for (int t = 0; t < CHOL_BS; ++t) P[tid][t] = row[t];
     }
     __syncthreads();
-    for (int idx = tid; idx < rows * CHOL_BS; idx += TPB) {
+    for (int idx = tid; idx < rows * CHOL_BS; idx += CHOL_PANEL_TPB) {
       const int r = idx / CHOL_BS, c = idx % CHOL_BS;
       Ab[(long long)(c0 + r) * N + k0 + c] = P[r][c];
     }
@@ -664,223 +571,20 @@ __device__ __forceinline__ void chol_panel_body(
   }
 }
 
-
-template <int GROUP_COLS, int TPB = CHOLP_TPB>
-__global__ __launch_bounds__(TPB) void chol_panel_kernel(
+__global__ __launch_bounds__(CHOL_PANEL_TPB) void chol_panel_kernel(
     float* __restrict__ A, float* __restrict__ logdet, int* __restrict__ info,
     int N, int k0, float* __restrict__ rhs) {
   __shared__ float S[CHOL_BS][CHOL_BS + 1];
-  __shared__ float colbuf4[GROUP_COLS][CHOL_BS];
-  __shared__ float P[TPB][CHOL_BS + 1];
+  __shared__ float colbuf[CHOL_GROUP_COLS][CHOL_BS];
+  __shared__ float P[CHOL_PANEL_TPB][CHOL_BS + 1];
   const int b = blockIdx.x;
-  chol_panel_body<GROUP_COLS, TPB>(
-      A + (long long)b * N * N, logdet + b, info + b, N, k0,
-      rhs ? rhs + (long long)b * N : nullptr, S, colbuf4, P);
+  chol_panel_body<false>(A + (long long)b * N * N, logdet + b, info + b, N, k0,
+                         rhs ? rhs + (long long)b * N : nullptr, S, colbuf, P);
 }
 
-// ------------------------------------------------------------ 64-wide panel
-// PANEL64 variant: one launch factors a 64x64 diagonal block (two wave-
-// parallel 32-factors + an in-LDS TRSM + SYRK between them) and solves the
-// whole 64-column panel below it. Halves the panel-launch count of the
-// right-looking loop (N=300: 5 launches instead of 10) — the multik path
-// is launch-gap bound at ~10 us fixed cost per launch (profiles/README.md).
-#define PANEL64 64
-
-// Factor the bs_ x bs_ (<=32) diagonal sub-block of S at offset (o, o):
-// wave-parallel, lane i owns row i in registers (same scheme as
-// chol_panel_kernel's diagonal factor). Caller must __syncthreads() after.
-__device__ __forceinline__ void factor32_at(
-    float S[PANEL64][PANEL64 + 1], float* colbuf, int o, int bs_,
-    float* logdet, int* info, int b, int gk0, int tid) {
-  if (tid < 64) {
-    const int lane = tid;
-    float r[CHOL_BS];
-#pragma unroll
-    for (int t = 0; t < CHOL_BS; ++t)
-      r[t] = (lane < bs_ && t < bs_) ? S[o + lane][o + t] : 0.0f;
-    float mylog = 0.0f;
-    int bad = 0;
-#pragma unroll
-    for (int j = 0; j < CHOL_BS; ++j) {
-      if (j >= bs_) continue;
-      float d = __shfl(r[j], j);
-      if (d <= 0.0f || !isfinite(d)) {
-        bad = bad ? bad : (gk0 + j + 1);
-        d = 1e-30f;
-      }
-      d = sqrtf(d);
-      if (lane == j) {
-        r[j] = d;
-        mylog = logf(d);
-      } else if (lane > j) {
-        r[j] /= d;
-      }
-      if (lane < bs_) colbuf[lane] = r[j];
-      __threadfence_block();
-#pragma unroll
-      for (int t = 0; t < CHOL_BS; ++t) {
-        if (t <= j || t >= bs_) continue;
-        if (lane >= t) r[t] = fmaf(-r[j], colbuf[t], r[t]);
-      }
-    }
-    if (lane < bs_) {
-#pragma unroll
-      for (int t = 0; t < CHOL_BS; ++t) {
-        if (t >= bs_) continue;
-        S[o + lane][o + t] = r[t];
-      }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-      mylog += __shfl_down(mylog, off);
-      const int ob = __shfl_down(bad, off);
-      bad = bad ? bad : ob;
-    }
-    if (lane == 0) {
-      logdet[b] += mylog;
-      if (bad && info[b] == 0) info[b] = bad;
-    }
-  }
-}
-
-#define P64_CHUNK 128  // panel rows staged per LDS buffer
-
-__global__ __launch_bounds__(CHOLP_TPB) void chol_panel64_kernel(
-    float* __restrict__ A, float* __restrict__ logdet, int* __restrict__ info,
-    int N, int k0) {
-  __shared__ float S[PANEL64][PANEL64 + 1];
-  __shared__ float colbuf[CHOL_BS];
-  __shared__ float P[P64_CHUNK][PANEL64 + 1];
-  const int b = blockIdx.x;
-  const int tid = threadIdx.x;
-  float* Ab = A + (long long)b * N * N;
-  const int bs = min(PANEL64, N - k0);
-  const int bs1 = min(CHOL_BS, bs);
-  const int bs2 = bs - bs1;
-
-  for (int idx = tid; idx < bs * bs; idx += blockDim.x)
-    S[idx / bs][idx % bs] = Ab[(long long)(k0 + idx / bs) * N + k0 + idx % bs];
-  __syncthreads();
-
-  factor32_at(S, colbuf, 0, bs1, logdet, info, b, k0, tid);
-  __syncthreads();
-
-  if (bs2 > 0) {
-    // TRSM: rows [32, bs) of columns [0, 32) against the factored block
-    if (tid < bs2) {
-      const int r = CHOL_BS + tid;
-#pragma unroll 4
-      for (int j = 0; j < CHOL_BS; ++j) {
-        float v = S[r][j];
-        for (int t = 0; t < j; ++t) v = fmaf(-S[r][t], S[j][t], v);
-        S[r][j] = v / S[j][j];
-      }
-    }
-    __syncthreads();
-    // SYRK the lower-right bs2 x bs2 block (lower triangle only: the
-    // factor routine never reads above the diagonal)
-    for (int idx = tid; idx < bs2 * bs2; idx += blockDim.x) {
-      const int i = idx / bs2, j = idx % bs2;
-      if (j > i) continue;
-      float acc = 0.0f;
-#pragma unroll 8
-      for (int k = 0; k < CHOL_BS; ++k)
-        acc = fmaf(S[CHOL_BS + i][k], S[CHOL_BS + j][k], acc);
-      S[CHOL_BS + i][CHOL_BS + j] -= acc;
-    }
-    __syncthreads();
-    factor32_at(S, colbuf, CHOL_BS, bs2, logdet, info, b, k0 + CHOL_BS, tid);
-    __syncthreads();
-  }
-
-  for (int idx = tid; idx < bs * bs; idx += blockDim.x) {
-    const int i = idx / bs, t = idx % bs;
-    if (t <= i) Ab[(long long)(k0 + i) * N + k0 + t] = S[i][t];
-  }
-
-  // 64-column panel solve below, staged through LDS in coalesced chunks
-  for (int c0 = k0 + PANEL64; c0 < N; c0 += P64_CHUNK) {
-    const int rows = min(P64_CHUNK, N - c0);
-    for (int idx = tid; idx < rows * PANEL64; idx += CHOLP_TPB) {
-      const int r = idx / PANEL64, c = idx % PANEL64;
-      P[r][c] = Ab[(long long)(c0 + r) * N + k0 + c];
-    }
-    __syncthreads();
-    if (tid < rows) {
-#pragma unroll 4
-      for (int j = 0; j < PANEL64; ++j) {
-        float v = P[tid][j];
-        for (int t = 0; t < j; ++t) v = fmaf(-P[tid][t], S[j][t], v);
-        P[tid][j] = v / S[j][j];
-      }
-    }
-    __syncthreads();
-    for (int idx = tid; idx < rows * PANEL64; idx += CHOLP_TPB) {
-      const int r = idx / PANEL64, c = idx % PANEL64;
-      Ab[(long long)(c0 + r) * N + k0 + c] = P[r][c];
-    }
-    __syncthreads();
-  }
-}
-
-// 64-deep trailing update: C -= Pi Pj^T with K = 64 (the PANEL64 step).
-// Same tile-pair enumeration as chol_syrk_kernel; k-loop runs the full 64
-// panel columns, so HALF the launches touch the same trailing bytes.
-__global__ __launch_bounds__(CHOLP_TPB) void chol_syrk64_kernel(
-    float* __restrict__ A, int N, int k0, int nt, int tj_fixed, int off) {
-  __shared__ float Pi[SYRK_TS][PANEL64];
-  __shared__ float Pj[SYRK_TS][PANEL64];
-  const int b = blockIdx.x;
-  float* Ab = A + (long long)b * N * N;
-  const int r0 = k0 + PANEL64;
-  int ti, tj;
-  if (tj_fixed >= 0) {
-    tj = tj_fixed;
-    ti = blockIdx.y + tj_fixed;
-  } else {
-    int p = blockIdx.y;
-    ti = 0;
-    while (p > ti) { p -= ti + 1; ++ti; }
-    tj = p + off;
-    ti += off;
-  }
-  const int i0 = r0 + ti * SYRK_TS, j0 = r0 + tj * SYRK_TS;
-  const int tid = threadIdx.x;
-
-  for (int idx = tid; idx < SYRK_TS * PANEL64; idx += blockDim.x) {
-    const int r = idx / PANEL64, c = idx % PANEL64;
-    const int cs = c ^ ((r & 7) << 2);  // bank-spread swizzle
-    Pi[r][cs] = (i0 + r < N) ? Ab[(long long)(i0 + r) * N + k0 + c] : 0.0f;
-    Pj[r][cs] = (j0 + r < N) ? Ab[(long long)(j0 + r) * N + k0 + c] : 0.0f;
-  }
-  __syncthreads();
-
-  typedef __attribute__((ext_vector_type(4))) float f32x4;
-  const int wave = tid >> 6, lane = tid & 63;
-  const int lr = lane & 15, lk = lane >> 4;
-#pragma unroll
-  for (int sIdx = 0; sIdx < 4; ++sIdx) {
-    const int sub = wave * 4 + sIdx;
-    const int r16 = (sub >> 2) * 16, c16 = (sub & 3) * 16;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < PANEL64; k += 4) {
-      const int ra = r16 + lr, rb = c16 + lr;
-      const float a = Pi[ra][(k + lk) ^ ((ra & 7) << 2)];
-      const float bv = Pj[rb][(k + lk) ^ ((rb & 7) << 2)];
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc, 0, 0, 0);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = i0 + r16 + lk * 4 + r;
-      const int j = j0 + c16 + lr;
-      if (i < N && j < N && j <= i) Ab[(long long)i * N + j] -= acc[r];
-    }
-  }
-}
-
-// Trailing update A[ti,tj] -= P_i P_j^T over 64x64 tiles of the submatrix
-// below/right of the panel; blockIdx.y enumerates lower-triangular tile
-// pairs, each 256-thread block computes a 4x4 register tile per thread.
+// Trailing update A[ti,tj] -= P_i P_j^T for one 64x64 tile (ti, tj) of the
+// submatrix below/right of the panel at k0: the block's first four waves
+// each compute four 16x16 MFMA sub-tiles.
 // r0 is the tile origin (first row and column the tiles cover): k0 + 32 for
 // the classic full trailing update, k0 + 64 for the look-ahead schedule's
 // role B, whose first 32 columns belong to role A's strip.
@@ -890,6 +594,11 @@ __device__ __forceinline__ void chol_syrk_tile_body(
   const int i0 = r0 + ti * SYRK_TS, j0 = r0 + tj * SYRK_TS;
   const int tid = threadIdx.x;
 
+  // Pi / Pj: stride 32 with an XOR swizzle on the k-column: the MFMA operand
+  // read (lane -> [row + lr][k + lk]) hits banks (row+lk) mod 32 under a +1
+  // pad, an up-to-8-way conflict (PMC: 2.2 extra cycles per LDS
+  // instruction); c = k ^ ((row & 7) << 2) spreads (lr, lk) over all 32
+  // banks.
   for (int idx = tid; idx < SYRK_TS * CHOL_BS; idx += blockDim.x) {
     const int r = idx / CHOL_BS, c = idx % CHOL_BS;
     const int cs = c ^ ((r & 7) << 2);  // swizzled physical column
@@ -898,8 +607,11 @@ __device__ __forceinline__ void chol_syrk_tile_body(
   }
   __syncthreads();
 
-  // MFMA tile core: C -= Pi * Pj^T on the matrix units (operand map and
-  // rationale in the original kernel comment below).
+  // MFMA tile core: C -= Pi * Pj^T on the matrix units.
+  // v_mfma_f32_16x16x4_f32 is EXACT fp32 (identical to an fmaf chain) at
+  // the f32 vector rate; operand map (cdna4_isa section 10):
+  // A: lane l -> A[l&15][l>>4]; B: lane l -> B[l>>4][l&15];
+  // C/D (f32x4): col = lane&15, row = (lane>>4)*4 + reg.
   const int wave = tid >> 6, lane = tid & 63;
   const int lr = lane & 15, lk = lane >> 4;
 #pragma unroll
@@ -918,8 +630,8 @@ __device__ __forceinline__ void chol_syrk_tile_body(
       if (i < N && j < N && j <= i) Ab[(long long)i * N + j] -= acc[r];
     }
   }
-  // fused-solve trailing update (diagonal tiles only); see original
-  // kernel comment.
+  // fused-solve trailing update: the diagonal tiles apply the panel's
+  // rank-32 update to their 64 rhs entries (scheme in chol_panel_body)
   if (rhs_b != nullptr && ti == tj && tid < 64) {
     const int i = i0 + tid;
     if (i < N) {
@@ -929,36 +641,17 @@ __device__ __forceinline__ void chol_syrk_tile_body(
   }
 }
 
-__global__ __launch_bounds__(CHOLP_TPB) void chol_syrk_kernel(
-    float* __restrict__ A, int N, int k0, int nt, int tj_fixed, int off,
-    float* __restrict__ rhs) {
-  // stride 32 with an XOR swizzle on the k-column: the MFMA operand read
-  // (lane -> [row + lr][k + lk]) hits banks (row+lk) mod 32 under a +1 pad,
-  // an up-to-8-way conflict (PMC: 2.2 extra cycles per LDS instruction);
-  // c = k ^ ((row & 7) << 2) spreads (lr, lk) over all 32 banks.
-  // v_mfma_f32_16x16x4_f32 is EXACT fp32 (identical to an fmaf chain) at
-  // the f32 vector rate; operand map (cdna4_isa section 10):
-  // A: lane l -> A[l&15][l>>4]; B: lane l -> B[l>>4][l&15];
-  // C/D (f32x4): col = lane&15, row = (lane>>4)*4 + reg.
+// Full trailing update of the classic schedule: grid (B, tile pairs),
+// blockIdx.y walks the lower triangle of 64x64 tiles from tile (0, 0) at
+// origin k0 + 32.
+__global__ __launch_bounds__(CHOL_SYRK_TPB) void chol_syrk_kernel(
+    float* __restrict__ A, int N, int k0, float* __restrict__ rhs) {
   __shared__ float Pi[SYRK_TS][CHOL_BS];
   __shared__ float Pj[SYRK_TS][CHOL_BS];
   const int b = blockIdx.x;
   float* Ab = A + (long long)b * N * N;
-  // tile-pair selection: tj_fixed >= 0 enumerates one tile COLUMN
-  // (ti = blockIdx.y + tj_fixed); otherwise blockIdx.y walks the lower
-  // triangle, shifted by `off` columns/rows (used to split the first tile
-  // column from the rest for cross-stream overlap)
   int ti, tj;
-  if (tj_fixed >= 0) {
-    tj = tj_fixed;
-    ti = blockIdx.y + tj_fixed;
-  } else {
-    int p = blockIdx.y;
-    ti = 0;
-    while (p > ti) { p -= ti + 1; ++ti; }
-    tj = p + off;
-    ti += off;
-  }
+  tri_tile_decode(blockIdx.y, &ti, &tj);
   chol_syrk_tile_body(Ab, N, k0, k0 + CHOL_BS, ti, tj,
                       rhs ? rhs + (long long)b * N : nullptr, Pi, Pj);
 }
@@ -981,28 +674,27 @@ __global__ __launch_bounds__(CHOLP_TPB) void chol_syrk_kernel(
 // those of the classic schedule bit for bit (shared inlines above).
 // Role B's tile buffers alias the panel's TRSM buffer P (a block has one
 // role), keeping the static LDS at the panel's ~55 KB + 4 KB for Lj.
-template <int GROUP_COLS, int TPB>
-__global__ __launch_bounds__(TPB) void chol_step_kernel(
+__global__ __launch_bounds__(CHOL_PANEL_TPB) void chol_step_kernel(
     float* __restrict__ A, float* __restrict__ logdet, int* __restrict__ info,
     int N, int k0, float* __restrict__ rhs) {
   __shared__ float S[CHOL_BS][CHOL_BS + 1];
-  __shared__ float colbuf4[GROUP_COLS][CHOL_BS];
-  __shared__ float P[TPB][CHOL_BS + 1];
+  __shared__ float colbuf[CHOL_GROUP_COLS][CHOL_BS];
+  __shared__ float P[CHOL_PANEL_TPB][CHOL_BS + 1];
   __shared__ float Lj[CHOL_BS + 1][CHOL_BS];  // + the solved rhs segment
-  static_assert(TPB * (CHOL_BS + 1) >= 2 * SYRK_TS * CHOL_BS,
+  static_assert(CHOL_PANEL_TPB * (CHOL_BS + 1) >= 2 * SYRK_TS * CHOL_BS,
                 "tile buffers must fit in the TRSM buffer");
   const int b = blockIdx.x;
   float* Ab = A + (long long)b * N * N;
   float* rhs_b = rhs ? rhs + (long long)b * N : nullptr;
   if (blockIdx.y == 0) {
-    chol_panel_body<GROUP_COLS, TPB, true>(Ab, logdet + b, info + b, N, k0,
-                                           rhs_b, S, colbuf4, P, Lj);
+    chol_panel_body<true>(Ab, logdet + b, info + b, N, k0, rhs_b, S, colbuf,
+                          P, Lj);
   } else {
     float(*Pi)[CHOL_BS] = (float(*)[CHOL_BS]) & P[0][0];
     float(*Pj)[CHOL_BS] = Pi + SYRK_TS;
-    int p = blockIdx.y - 1, ti = 0;
-    while (p > ti) { p -= ti + 1; ++ti; }
-    chol_syrk_tile_body(Ab, N, k0 - CHOL_BS, k0 + CHOL_BS, ti, p, rhs_b, Pi,
+    int ti, tj;
+    tri_tile_decode(blockIdx.y - 1, &ti, &tj);
+    chol_syrk_tile_body(Ab, N, k0 - CHOL_BS, k0 + CHOL_BS, ti, tj, rhs_b, Pi,
                         Pj);
   }
 }
@@ -1124,8 +816,6 @@ __global__ void backward_solve_batched_kernel(const float* __restrict__ L,
   }
 }
 
-#include <stdlib.h>
-
 // Final NMLL assembly: out[b] = 0.5 * sum(Z_b^2) + half_logdet[b] + c,
 // inf where the factorization failed or the value is non-finite — fuses the
 // (z*z).sum + scalar-combine + masking chain (a handful of torch dispatches
@@ -1159,77 +849,42 @@ extern "C" void launch_nmll_reduce(const float* Z, const float* half_logdet,
                      half_logdet, info, out, N, c);
 }
 
-__global__ void zero_i32_kernel(int* __restrict__ p, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = 0;
-}
-
 __global__ void zero_f32_kernel(float* __restrict__ p, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = 0.0f;
 }
 
-// panel-group-size selection: 2- vs 4-column factor rounds, same-box A/B
-// via DMOSOPT_CHOL_GROUP (bitwise-identical results either way)
-static inline int panel_group_cols() {
-  static int g = -1;
-  if (g < 0) {
-    const char* e = getenv("DMOSOPT_CHOL_GROUP");
-    // 2 (default) / 4 = grouped LDS-broadcast factor rounds; 1 = pure-
-    // shuffle factor, measured 2.5x SLOWER (804 vs 324 us per B=12 chol,
-    // same box): __shfl is ds_bpermute on CDNA4 — a full LDS round trip
-    // per value — so 512 dependent shuffles lose to 16 fence-paired LDS
-    // column broadcasts. Kept selectable for re-measurement.
-    g = e ? atoi(e) : 2;
-    if (g != 1 && g != 4) g = 2;
-  }
-  return g;
+// logdet accumulates across the panel launches, so every multik entry zeroes
+// it first. An explicit zero KERNEL instead of hipMemsetAsync: under hipGraph
+// stream capture (models/gp_core.py _NmllGraph) the captured memset node was
+// observed to race with the first panel kernel's logdet accumulation on
+// replay (bit-nondeterministic outputs with bit-identical inputs,
+// scripts_det_debug6.py); a kernel node orders correctly.
+static inline void launch_zero_logdet(float* logdet, int B,
+                                      hipStream_t stream) {
+  hipLaunchKernelGGL(zero_f32_kernel, dim3((B + 255) / 256), dim3(256), 0,
+                     stream, logdet, B);
 }
-// panel workgroup width: 384 threads solve the whole N=300 trailing panel
-// in ONE LDS chunk (256 needs two sequential chunk rounds: stage + solve +
-// writeback + 3 barriers each); static LDS caps the width at 384
-// (P[384][33] + S + colbuf = 55 KB < 64 KB). Same-box A/B via
-// DMOSOPT_CHOL_TPB.
-static inline int panel_tpb() {
-  static int t = -1;
-  if (t < 0) {
-    const char* e = getenv("DMOSOPT_CHOL_TPB");
-    t = (e && atoi(e) == 256) ? 256 : 384;
-  }
-  return t;
-}
-#define LAUNCH_PANEL(B_, stream_, A_, logdet_, info_, N_, k0_, rhs_)                 do {                                                                           const int tpb_ = panel_tpb();                                                if (panel_group_cols() == 1) {                                                 if (tpb_ == 384)                                                               hipLaunchKernelGGL((chol_panel_kernel<1, 384>), dim3(B_), dim3(384),                            0, stream_, A_, logdet_, info_, N_, k0_, rhs_);             else                                                                           hipLaunchKernelGGL((chol_panel_kernel<1, 256>), dim3(B_), dim3(256),                            0, stream_, A_, logdet_, info_, N_, k0_, rhs_);           } else if (panel_group_cols() == 2) {                                                 if (tpb_ == 384)                                                               hipLaunchKernelGGL((chol_panel_kernel<2, 384>), dim3(B_), dim3(384),                            0, stream_, A_, logdet_, info_, N_, k0_, rhs_);             else                                                                           hipLaunchKernelGGL((chol_panel_kernel<2, 256>), dim3(B_), dim3(256),                            0, stream_, A_, logdet_, info_, N_, k0_, rhs_);           } else {                                                                       if (tpb_ == 384)                                                               hipLaunchKernelGGL((chol_panel_kernel<4, 384>), dim3(B_), dim3(384),                            0, stream_, A_, logdet_, info_, N_, k0_, rhs_);             else                                                                           hipLaunchKernelGGL((chol_panel_kernel<4, 256>), dim3(B_), dim3(256),                            0, stream_, A_, logdet_, info_, N_, k0_, rhs_);           }                                                                          } while (0)
 
-template <int GROUP_COLS, int TPB>
-static inline void launch_chol_step_gt(dim3 grid, hipStream_t stream, float* A,
-                                       float* logdet, int* info, int N, int k0,
-                                       float* rhs) {
-  hipLaunchKernelGGL((chol_step_kernel<GROUP_COLS, TPB>), grid, dim3(TPB), 0,
+// Plain panel launch, shared by the classic schedule, panel 0 of the
+// look-ahead schedule and the bf16 path.
+static inline void launch_chol_panel(float* A, float* logdet, int* info,
+                                     float* rhs, int B, int N, int k0,
+                                     hipStream_t stream) {
+  hipLaunchKernelGGL(chol_panel_kernel, dim3(B), dim3(CHOL_PANEL_TPB), 0,
                      stream, A, logdet, info, N, k0, rhs);
 }
 
-// look-ahead step launch under the same group / width switches as the panel
-static inline void launch_chol_step(int B, int tiles, hipStream_t stream,
-                                    float* A, float* logdet, int* info, int N,
-                                    int k0, float* rhs) {
-  const dim3 grid(B, 1 + tiles);
-  const bool wide = panel_tpb() == 384;
-  switch (panel_group_cols()) {
-    case 1:
-      if (wide) launch_chol_step_gt<1, 384>(grid, stream, A, logdet, info, N, k0, rhs);
-      else launch_chol_step_gt<1, 256>(grid, stream, A, logdet, info, N, k0, rhs);
-      break;
-    case 2:
-      if (wide) launch_chol_step_gt<2, 384>(grid, stream, A, logdet, info, N, k0, rhs);
-      else launch_chol_step_gt<2, 256>(grid, stream, A, logdet, info, N, k0, rhs);
-      break;
-    default:
-      if (wide) launch_chol_step_gt<4, 384>(grid, stream, A, logdet, info, N, k0, rhs);
-      else launch_chol_step_gt<4, 256>(grid, stream, A, logdet, info, N, k0, rhs);
-  }
+// 64x64 lower-triangle tile pairs of the trailing matrix that starts at r0
+// (0 when nothing is left).
+static inline int chol_tile_pairs(int N, int r0) {
+  const int trailing = N - r0;
+  if (trailing <= 0) return 0;
+  const int nt = (trailing + SYRK_TS - 1) / SYRK_TS;
+  return nt * (nt + 1) / 2;
 }
 
-// trailing-update schedule of the 32-wide multik path:
+// trailing-update schedule of the multik path:
 //   classic    — panel launch, then a full-matrix SYRK launch, per step;
 //   look-ahead — plain panel 0, then ONE chol_step_kernel launch per
 //                remaining panel (bitwise-identical results).
@@ -1249,38 +904,34 @@ static inline int chol_lookahead_default() {
 static void chol_multik_classic(float* A, float* logdet, int* info,
                                 float* rhs, int B, int N, hipStream_t stream) {
   for (int k0 = 0; k0 < N; k0 += CHOL_BS) {
-    LAUNCH_PANEL(B, stream, A, logdet, info, N, k0, rhs);
-    const int trailing = N - k0 - CHOL_BS;
-    if (trailing > 0) {
-      const int nt = (trailing + SYRK_TS - 1) / SYRK_TS;
-      hipLaunchKernelGGL(chol_syrk_kernel, dim3(B, nt * (nt + 1) / 2),
-                         dim3(CHOLP_TPB), 0, stream, A, N, k0, nt, -1, 0,
-                         rhs);
-    }
+    launch_chol_panel(A, logdet, info, rhs, B, N, k0, stream);
+    const int pairs = chol_tile_pairs(N, k0 + CHOL_BS);
+    if (pairs > 0)
+      hipLaunchKernelGGL(chol_syrk_kernel, dim3(B, pairs),
+                         dim3(CHOL_SYRK_TPB), 0, stream, A, N, k0, rhs);
   }
 }
 
 static void chol_multik_lookahead(float* A, float* logdet, int* info,
                                   float* rhs, int B, int N,
                                   hipStream_t stream) {
-  LAUNCH_PANEL(B, stream, A, logdet, info, N, 0, rhs);
+  launch_chol_panel(A, logdet, info, rhs, B, N, 0, stream);
   for (int k0 = CHOL_BS; k0 < N; k0 += CHOL_BS) {
     // role B covers rows/columns >= k0 + 32; none left on the last steps
-    const int trailing = N - k0 - CHOL_BS;
-    const int nt = trailing > 0 ? (trailing + SYRK_TS - 1) / SYRK_TS : 0;
-    launch_chol_step(B, nt * (nt + 1) / 2, stream, A, logdet, info, N, k0,
-                     rhs);
+    const int pairs = chol_tile_pairs(N, k0 + CHOL_BS);
+    hipLaunchKernelGGL(chol_step_kernel, dim3(B, 1 + pairs),
+                       dim3(CHOL_PANEL_TPB), 0, stream, A, logdet, info, N,
+                       k0, rhs);
   }
 }
 
 // Explicit-schedule entry (tests and isolated timing compare the two
-// schedules inside one process; the env switches are latched).
+// schedules inside one process; the env switch is latched).
 extern "C" void launch_cholesky_multik_sched(float* A, float* logdet,
                                              int* info, float* rhs, int B,
                                              int N, int sched,
                                              hipStream_t stream) {
-  hipLaunchKernelGGL(zero_f32_kernel, dim3((B + 255) / 256), dim3(256), 0,
-                     stream, logdet, B);
+  launch_zero_logdet(logdet, B, stream);
   if (sched == CHOL_SCHED_LOOKAHEAD)
     chol_multik_lookahead(A, logdet, info, rhs, B, N, stream);
   else
@@ -1290,282 +941,49 @@ extern "C" void launch_cholesky_multik_sched(float* A, float* logdet,
 extern "C" void launch_cholesky_multik(float* A, float* logdet, int* info,
                                        float* rhs, int B, int N,
                                        hipStream_t stream) {
-  // Cross-stream software pipeline: panel(k+1) only depends on the FIRST
-  // tile column of step k's trailing update (its 64 columns cover the next
-  // panel), so the remaining tile pairs run on a side stream concurrently
-  // with the next panel. Regions are disjoint: tj0(k) writes cols
-  // [k0+32, k0+95]; rest(k) writes cols >= k0+96; panel(k+1) writes cols
-  // [k0+32, k0+63] AFTER tj0(k) on the main stream.
-  static int overlap = -1;
-  static hipStream_t s2 = nullptr;
-  static hipEvent_t evP[2], evR[2];
-  if (overlap < 0) {
-    // measured NEGATIVE at B=12..192 / N=300 (477 vs 386 us per call):
-    // the cross-stream event waits cost more than the ~90 us of SYRK they
-    // hide. Kept opt-in for larger shapes: DMOSOPT_CHOL_OVERLAP=1.
-    const char* env = getenv("DMOSOPT_CHOL_OVERLAP");
-    overlap = (env && env[0] == '1') ? 1 : 0;
-    if (overlap) {
-      hipStreamCreateWithFlags(&s2, hipStreamNonBlocking);
-      for (int i = 0; i < 2; ++i) {
-        hipEventCreateWithFlags(&evP[i], hipEventDisableTiming);
-        hipEventCreateWithFlags(&evR[i], hipEventDisableTiming);
-      }
-    }
-  }
-  // explicit zero KERNEL instead of hipMemsetAsync: under hipGraph stream
-  // capture (models/gp_core.py _NmllGraph) the captured memset node was
-  // observed to race with the first panel kernel's logdet accumulation on
-  // replay (bit-nondeterministic outputs with bit-identical inputs,
-  // scripts_det_debug6.py); a kernel node orders correctly
-  hipLaunchKernelGGL(zero_f32_kernel, dim3((B + 255) / 256), dim3(256), 0,
-                     stream, logdet, B);
-  static int panel64 = -1;
-  if (panel64 < 0) {
-    // measured WORSE than PANEL32 across the board (profiles/README.md:
-    // 0.89 vs 0.41 ms at B=12 N=300; 7x at N=4096): the in-kernel
-    // TRSM/SYRK serial phases and the 64-deep per-row solve chain cost far
-    // more than the ~10 us/launch the halved launch count saves. Kept as
-    // DMOSOPT_CHOL_PANEL=64 for re-measurement on future ROCm/driver.
-    const char* env = getenv("DMOSOPT_CHOL_PANEL");
-    panel64 = (env && env[0] == '6') ? 1 : 0;
-  }
-  if (panel64 && !overlap) {
-    for (int k0 = 0; k0 < N; k0 += PANEL64) {
-      hipLaunchKernelGGL(chol_panel64_kernel, dim3(B), dim3(CHOLP_TPB), 0,
-                         stream, A, logdet, info, N, k0);
-      const int trailing = N - k0 - PANEL64;
-      if (trailing > 0) {
-        const int nt = (trailing + SYRK_TS - 1) / SYRK_TS;
-        hipLaunchKernelGGL(chol_syrk64_kernel, dim3(B, nt * (nt + 1) / 2),
-                           dim3(CHOLP_TPB), 0, stream, A, N, k0, nt, -1, 0);
-      }
-    }
-    return;
-  }
-  if (!overlap) {
-    if (chol_lookahead_default())
-      chol_multik_lookahead(A, logdet, info, rhs, B, N, stream);
-    else
-      chol_multik_classic(A, logdet, info, rhs, B, N, stream);
-    return;
-  }
-  int kstep = 0;
-  bool have_rest_prev = false;
-  // the overlap path does not carry a fused rhs (launch_cholesky_fused_solve
-  // refuses it): the tj0/rest split would double-apply the diagonal tiles
-  for (int k0 = 0; k0 < N; k0 += CHOL_BS, ++kstep) {
-    LAUNCH_PANEL(B, stream, A, logdet, info, N, k0, nullptr);
-    const int trailing = N - k0 - CHOL_BS;
-    if (trailing <= 0) continue;
-    const int nt = (trailing + SYRK_TS - 1) / SYRK_TS;
-    const int slot = kstep & 1;
-    if (nt > 1) hipEventRecord(evP[slot], stream);
-    // tj0(k) waits for rest(k-1): their column regions overlap
-    if (have_rest_prev) hipStreamWaitEvent(stream, evR[slot ^ 1], 0);
-    hipLaunchKernelGGL(chol_syrk_kernel, dim3(B, nt), dim3(CHOLP_TPB), 0,
-                       stream, A, N, k0, nt, 0, 0, nullptr);
-    if (nt > 1) {
-      const int rest_pairs = (nt - 1) * nt / 2;
-      hipStreamWaitEvent(s2, evP[slot], 0);
-      hipLaunchKernelGGL(chol_syrk_kernel, dim3(B, rest_pairs),
-                         dim3(CHOLP_TPB), 0, s2, A, N, k0, nt, -1, 1,
-                         nullptr);
-      hipEventRecord(evR[slot], s2);
-      have_rest_prev = true;
-    } else {
-      have_rest_prev = false;
-    }
-  }
-  // rejoin the side stream before anything downstream reads the factor
-  if (have_rest_prev) hipStreamWaitEvent(stream, evR[(kstep - 1) & 1], 0);
+  launch_cholesky_multik_sched(
+      A, logdet, info, rhs, B, N,
+      chol_lookahead_default() ? CHOL_SCHED_LOOKAHEAD : CHOL_SCHED_CLASSIC,
+      stream);
 }
 
-
-
-// ------------------------------------------------ persistent whole-chol
-// ONE launch factorizes all B matrices: grid (B, 1 + T). Block (b, 0) is
-// matrix b's PANEL block — it loops the right-looking steps, running the
-// shared chol_panel_body per step; blocks (b, 1..T) are its SYRK TILE
-// blocks. Steps hand off through two per-matrix device-scope flags
-// (panel_flag counts completed panels, tiles_done counts completed tiles
-// cumulatively — monotone counters, so no reset races):
-//   tiles of step s spin until panel_flag >= s+1, then update their
-//   64x64 trailing tile; the panel of step s+1 spins until tiles_done ==
-//   cumulative pairs through step s. Replaces 2*ceil(N/32)-1 dispatches
-//   (each ~5-8 us of entry/exit on this stack even inside a hipGraph)
-//   with intra-kernel handoffs. DEADLOCK SAFETY: the launcher verifies
-//   full-grid residency via the occupancy API (all blocks co-resident by
-//   construction), and both spin loops are BOUNDED — on timeout they
-//   stamp info[b] and exit instead of hanging the device.
-#define PERSIST_TPB 384
-
-static __device__ __forceinline__ int persist_pairs(int N, int k0) {
-  const int trailing = N - k0 - CHOL_BS;
-  if (trailing <= 0) return 0;
-  const int nt = (trailing + SYRK_TS - 1) / SYRK_TS;
-  return nt * (nt + 1) / 2;
-}
-
-__global__ __launch_bounds__(PERSIST_TPB) void chol_persist_kernel(
-    float* __restrict__ A, float* __restrict__ logdet, int* __restrict__ info,
-    float* __restrict__ rhs, int* __restrict__ ws, int N) {
-  extern __shared__ char smem[];
-  const int b = blockIdx.x;
-  const int role = blockIdx.y;  // 0 = panel block, >=1 = tile block role-1
-  const int tid = threadIdx.x;
-  float* Ab = A + (long long)b * N * N;
-  float* rhs_b = rhs ? rhs + (long long)b * N : nullptr;
-  int* panel_flag = ws + 2 * b;
-  int* tiles_done = ws + 2 * b + 1;
-
-  if (role == 0) {
-    float(*S)[CHOL_BS + 1] = (float(*)[CHOL_BS + 1])smem;
-    float(*colbuf)[CHOL_BS] =
-        (float(*)[CHOL_BS])(smem + sizeof(float) * CHOL_BS * (CHOL_BS + 1));
-    float(*P)[CHOL_BS + 1] =
-        (float(*)[CHOL_BS + 1])(smem + sizeof(float) * (CHOL_BS * (CHOL_BS + 1) +
-                                                        2 * CHOL_BS));
-    int cum = 0;
-    for (int k0 = 0, step = 0; k0 < N; k0 += CHOL_BS, ++step) {
-      if (step > 0) {
-        if (tid == 0) {
-          long long it = 0;
-          while (atomicAdd(tiles_done, 0) < cum) {
-            __builtin_amdgcn_s_sleep(8);
-            if (++it > 5000000LL) {  // ~1 s at ~512 cycles per sleep(8)  // bounded: fail loudly, not a hang
-              if (atomicCAS(info + b, 0, -777) == 0) {}
-              break;
-            }
-          }
-        }
-        __syncthreads();
-        __threadfence();  // acquire: invalidate L1 before reading tiles' output
-        if (*(volatile int*)(info + b) < 0) return;  // timeout sentinel
-      }
-      chol_panel_body<2, PERSIST_TPB>(Ab, logdet + b, info + b, N, k0, rhs_b,
-                                      S, colbuf, P);
-      __threadfence();  // release: panel writes visible device-wide
-      __syncthreads();
-      if (tid == 0) atomicExch(panel_flag, step + 1);
-      cum += persist_pairs(N, k0);
-    }
-  } else {
-    float(*Pi)[CHOL_BS] = (float(*)[CHOL_BS])smem;
-    float(*Pj)[CHOL_BS] =
-        (float(*)[CHOL_BS])(smem + sizeof(float) * SYRK_TS * CHOL_BS);
-    const int t = role - 1;
-    for (int k0 = 0, step = 0; k0 < N; k0 += CHOL_BS, ++step) {
-      const int pairs = persist_pairs(N, k0);
-      if (t >= pairs) continue;  // no tile for this block at this step
-      if (tid == 0) {
-        long long it = 0;
-        while (atomicAdd(panel_flag, 0) < step + 1) {
-          __builtin_amdgcn_s_sleep(8);
-          if (++it > 5000000LL) {  // ~1 s at ~512 cycles per sleep(8)
-            if (atomicCAS(info + b, 0, -778) == 0) {}
-            break;
-          }
-        }
-      }
-      __syncthreads();
-      __threadfence();  // acquire before reading the panel output
-      if (*(volatile int*)(info + b) < 0) return;  // timeout sentinel
-      int p = t, ti = 0;
-      while (p > ti) { p -= ti + 1; ++ti; }
-      const int tj = p;
-      chol_syrk_tile_body(Ab, N, k0, k0 + CHOL_BS, ti, tj, rhs_b, Pi, Pj);
-      __threadfence();  // release tile writes
-      __syncthreads();
-      if (tid == 0) atomicAdd(tiles_done, 1);
-    }
-  }
-}
-
-extern "C" int launch_cholesky_persist(float* A, float* logdet, int* info,
-                                       float* rhs, int* ws, int B, int N,
-                                       hipStream_t stream) {
-  // only the default panel configuration is instantiated
-  if (panel_group_cols() != 2) return -1;
-  const int trailing0 = N - CHOL_BS;
-  if (trailing0 <= 0) return -1;
-  const int nt0 = (trailing0 + SYRK_TS - 1) / SYRK_TS;
-  const int T = nt0 * (nt0 + 1) / 2;
-  const size_t lds = sizeof(float) * (CHOL_BS * (CHOL_BS + 1) + 2 * CHOL_BS +
-                                      PERSIST_TPB * (CHOL_BS + 1));
-  static int max_resident = -1;
-  if (max_resident < 0) {
-    hipFuncSetAttribute((const void*)chol_persist_kernel,
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    int per_cu = 0;
-    hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &per_cu, (const void*)chol_persist_kernel, PERSIST_TPB, lds);
-    hipDeviceProp_t prop;
-    int dev = 0;
-    hipGetDevice(&dev);
-    hipGetDeviceProperties(&prop, dev);
-    max_resident = per_cu * prop.multiProcessorCount;
-  }
-  // DEADLOCK GUARD: every block must be co-resident for the spin handoffs
-  if ((long long)B * (1 + T) > max_resident) return -1;
-  hipLaunchKernelGGL(zero_i32_kernel, dim3((2 * B + 255) / 256), dim3(256), 0,
-                     stream, ws, 2 * B);
-  hipLaunchKernelGGL(zero_f32_kernel, dim3((B + 255) / 256), dim3(256), 0,
-                     stream, logdet, B);
-  hipLaunchKernelGGL(chol_persist_kernel, dim3(B, 1 + T), dim3(PERSIST_TPB),
-                     lds, stream, A, logdet, info, rhs, ws, N);
-  return 0;
-}
-
-// bf16-SYRK variant of the right-looking multik path (config-#2 precision
-// route): panels factor in exact fp32 (chol_panel_kernel), only the
-// trailing C -= P P^T runs on the bf16 matrix units (matern_bf16.hip).
-extern "C" void launch_chol_syrk_bf16(float*, int, int, int, int, int, int,
-                                      int, hipStream_t);
+// bf16-SYRK variant of the classic schedule (config-#2 precision route):
+// panels factor in exact fp32 (chol_panel_kernel), only the trailing
+// C -= P P^T runs on the bf16 matrix units (matern_bf16.hip).
+extern "C" void launch_chol_syrk_bf16(float*, int, int, int, int,
+                                      hipStream_t);
 
 extern "C" void launch_cholesky_multik_bf16(float* A, float* logdet,
                                             int* info, int B, int N,
                                             hipStream_t stream) {
-  hipLaunchKernelGGL(zero_f32_kernel, dim3((B + 255) / 256), dim3(256), 0,
-                     stream, logdet, B);
+  launch_zero_logdet(logdet, B, stream);
   for (int k0 = 0; k0 < N; k0 += CHOL_BS) {
-    LAUNCH_PANEL(B, stream, A, logdet, info, N, k0, nullptr);
-    const int trailing = N - k0 - CHOL_BS;
-    if (trailing > 0) {
-      const int nt = (trailing + SYRK_TS - 1) / SYRK_TS;
-      launch_chol_syrk_bf16(A, N, k0, nt, -1, 0, nt * (nt + 1) / 2, B,
-                            stream);
-    }
+    launch_chol_panel(A, logdet, info, nullptr, B, N, k0, stream);
+    const int pairs = chol_tile_pairs(N, k0 + CHOL_BS);
+    if (pairs > 0) launch_chol_syrk_bf16(A, N, k0, pairs, B, stream);
   }
 }
 
-extern "C" int launch_cholesky_persist(float*, float*, int*, float*, int*,
-                                       int, int, hipStream_t);
+// Up to this batch count the one-block-per-matrix kernel cannot fill the 256
+// CUs, so the multi-launch path wins. DMOSOPT_CHOL_MODE=single|multik
+// overrides the choice for A/B measurement.
+#define CHOL_MULTIK_MAX_B 48
 
+// Factor with the forward solve of rhs (B, N) fused into the multik launch
+// chain. Returns -1 without launching anything when the multik path does not
+// apply (DMOSOPT_CHOL_MODE=single, DMOSOPT_CHOL_FUSED_SOLVE=0, a single
+// panel, or a batch large enough for the one-block-per-matrix kernel); the
+// caller then factors and solves separately.
 extern "C" int launch_cholesky_fused_solve(float* A, float* logdet,
-                                           int* info, float* rhs, int* ws,
-                                           int B, int N, hipStream_t stream) {
-  static int ok = -2;
-  static int persist_on = -1;
-  if (ok == -2) {
+                                           int* info, float* rhs, int B,
+                                           int N, hipStream_t stream) {
+  static int ok = -1;
+  if (ok < 0) {
     const char* m = getenv("DMOSOPT_CHOL_MODE");
-    const char* o = getenv("DMOSOPT_CHOL_OVERLAP");
-    const char* p = getenv("DMOSOPT_CHOL_PANEL");
     const char* f = getenv("DMOSOPT_CHOL_FUSED_SOLVE");
-    ok = ((m && m[0] == 's') || (o && o[0] == '1') || (p && p[0] == '6') ||
-          (f && f[0] == '0'))
-             ? 0
-             : 1;
-    // measured 205 vs 136 ms/epoch (same box, bit-identical HV): the
-    // intra-kernel handoffs + pointer-based LDS codegen cost far more
-    // than the ~16 saved dispatches. Kept as an opt-in experiment.
-    const char* pe = getenv("DMOSOPT_CHOL_PERSIST");
-    persist_on = (pe && pe[0] == '1') ? 1 : 0;
+    ok = ((m && m[0] == 's') || (f && f[0] == '0')) ? 0 : 1;
   }
-  if (!ok || N <= CHOL_BS || B > 48) return -1;
-  if (persist_on && ws != nullptr &&
-      launch_cholesky_persist(A, logdet, info, rhs, ws, B, N, stream) == 0)
-    return 0;
+  if (!ok || N <= CHOL_BS || B > CHOL_MULTIK_MAX_B) return -1;
   launch_cholesky_multik(A, logdet, info, rhs, B, N, stream);
   return 0;
 }
@@ -1574,38 +992,24 @@ extern "C" void launch_cholesky_batched(float* A, float* logdet, int* info,
                                         int B, int N, hipStream_t stream) {
   static int multik_max_b = -2;
   if (multik_max_b == -2) {
-    // below this batch count the one-block-per-matrix kernel cannot fill
-    // the 256 CUs, so the multi-launch right-looking path wins; override
-    // with DMOSOPT_CHOL_MODE=single|multik for A/B measurement
     const char* env = getenv("DMOSOPT_CHOL_MODE");
     if (env && env[0] == 's') multik_max_b = 0;
     else if (env && env[0] == 'm') multik_max_b = 1 << 30;
-    else multik_max_b = 48;
+    else multik_max_b = CHOL_MULTIK_MAX_B;
   }
   if (B <= multik_max_b && N > CHOL_BS) {
     launch_cholesky_multik(A, logdet, info, nullptr, B, N, stream);
     return;
   }
-  static int mode = -1;
-  if (mode < 0) {
-    // same-box A/B (profiles/README.md): LDS/barrier diag factor measured
-    // 0.80 ms vs 1.27 ms wave-sync at B=18, N=300 — LDS is the default;
-    // DMOSOPT_CHOL_DIAG=wave selects the wave-synchronous variant.
-    const char* env = getenv("DMOSOPT_CHOL_DIAG");
-    mode = (env && env[0] == 'w') ? 1 : 0;
-    hipFuncSetAttribute((const void*)cholesky_batched_kernel<true>,
+  static bool lds_attr_set = false;
+  if (!lds_attr_set) {
+    hipFuncSetAttribute((const void*)cholesky_batched_kernel,
                         hipFuncAttributeMaxDynamicSharedMemorySize,
                         (int)sizeof(CholLds));
-    hipFuncSetAttribute((const void*)cholesky_batched_kernel<false>,
-                        hipFuncAttributeMaxDynamicSharedMemorySize,
-                        (int)sizeof(CholLds));
+    lds_attr_set = true;
   }
-  if (mode)
-    hipLaunchKernelGGL(cholesky_batched_kernel<true>, dim3(B), dim3(CHOL_TPB),
-                       sizeof(CholLds), stream, A, logdet, info, N);
-  else
-    hipLaunchKernelGGL(cholesky_batched_kernel<false>, dim3(B), dim3(CHOL_TPB),
-                       sizeof(CholLds), stream, A, logdet, info, N);
+  hipLaunchKernelGGL(cholesky_batched_kernel, dim3(B), dim3(CHOL_TPB),
+                     sizeof(CholLds), stream, A, logdet, info, N);
 }
 
 extern "C" void launch_forward_solve_batched(const float* L, float* Y, int B,

@@ -19,6 +19,16 @@ __device__ __forceinline__ float warp_reduce_max(float v) {
   return v;
 }
 
+// Linear index p over the lower triangle, row by row ((0,0), (1,0), (1,1),
+// (2,0), ...), to its tile pair: row *ti >= column *tj. The Cholesky
+// trailing-update kernels enumerate their tile grids with it.
+__device__ __forceinline__ void tri_tile_decode(int p, int* ti, int* tj) {
+  int row = 0;
+  while (p > row) { p -= row + 1; ++row; }
+  *ti = row;
+  *tj = p;
+}
+
 // ---------------------------------------------------------------- Philox4x32
 // Counter-based RNG (Salmon et al. 2011), 10 rounds. Each call site derives
 // independent streams from (seed, counter) — the per-kernel RNG discipline

@@ -186,7 +186,7 @@ extern "C" void launch_matern_cross_bf16(const float* Xq, const float* X,
 #define BS16_TPB 256
 
 __global__ __launch_bounds__(BS16_TPB) void chol_syrk_bf16_kernel(
-    float* __restrict__ A, int N, int k0, int nt, int tj_fixed, int off) {
+    float* __restrict__ A, int N, int k0) {
   // bf16 panels: row stride 40 shorts (80 B) staggers the 16-byte fragment
   // reads of consecutive rows across bank groups
   __shared__ __bf16 Pi[BS16_SYRK_TS][BS16_CHOL_BS + 8];
@@ -195,16 +195,7 @@ __global__ __launch_bounds__(BS16_TPB) void chol_syrk_bf16_kernel(
   float* Ab = A + (long long)b * N * N;
   const int r0 = k0 + BS16_CHOL_BS;
   int ti, tj;
-  if (tj_fixed >= 0) {
-    tj = tj_fixed;
-    ti = blockIdx.y + tj_fixed;
-  } else {
-    int p = blockIdx.y;
-    ti = 0;
-    while (p > ti) { p -= ti + 1; ++ti; }
-    tj = p + off;
-    ti += off;
-  }
+  tri_tile_decode(blockIdx.y, &ti, &tj);
   const int i0 = r0 + ti * BS16_SYRK_TS, j0 = r0 + tj * BS16_SYRK_TS;
   const int tid = threadIdx.x;
 
@@ -235,9 +226,8 @@ __global__ __launch_bounds__(BS16_TPB) void chol_syrk_bf16_kernel(
   }
 }
 
-extern "C" void launch_chol_syrk_bf16(float* A, int N, int k0, int nt,
-                                      int tj_fixed, int off, int n_pairs,
+extern "C" void launch_chol_syrk_bf16(float* A, int N, int k0, int n_pairs,
                                       int B, hipStream_t stream) {
   hipLaunchKernelGGL(chol_syrk_bf16_kernel, dim3(B, n_pairs),
-                     dim3(BS16_TPB), 0, stream, A, N, k0, nt, tj_fixed, off);
+                     dim3(BS16_TPB), 0, stream, A, N, k0);
 }

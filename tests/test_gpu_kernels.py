@@ -51,11 +51,10 @@ def test_matern_cross_aniso_matches_torch(dev):
     assert torch.allclose(K_native.double(), K_ref, atol=5e-5)
 
 
-def test_cholesky_batched_matches_torch(dev):
+def _check_cholesky_batched(dev, B, N):
     from dmosopt_amd import _hipops
 
     g = torch.Generator().manual_seed(2)
-    B, N = 4, 300
     A = torch.randn(B, N, 8, generator=g)
     K = (A @ A.transpose(1, 2) + 0.5 * torch.eye(N)).float().to(dev).contiguous()
     L_ref = torch.linalg.cholesky(K.double().cpu())
@@ -63,8 +62,26 @@ def test_cholesky_batched_matches_torch(dev):
     Kc = K.clone()
     logdet, info = _hipops.cholesky_batched_(Kc)
     assert (info == 0).all()
-    assert torch.allclose(Kc.double().cpu().tril(), L_ref, atol=2e-3, rtol=1e-3)
-    assert torch.allclose(logdet.double().cpu(), logdet_ref, rtol=1e-4)
+    L = Kc.double().cpu().tril()
+    ld = logdet.double().cpu()
+    print(f"B={B} N={N}: max |L - L_ref| = {(L - L_ref).abs().max():.3e}, "
+          f"max rel logdet err = {((ld - logdet_ref) / logdet_ref).abs().max():.3e}")
+    assert torch.allclose(L, L_ref, atol=2e-3, rtol=1e-3)
+    assert torch.allclose(ld, logdet_ref, rtol=1e-4)
+
+
+def test_cholesky_batched_matches_torch(dev):
+    _check_cholesky_batched(dev, B=4, N=300)
+
+
+@pytest.mark.parametrize("N", [33, 97, 449])
+def test_cholesky_single_block_matches_torch(dev, N):
+    """B = 49 is the first batch size routed to the one-block-per-matrix
+    kernel (B = 4 above takes the multi-launch path). N = 33: one full
+    32-column block plus a 1-column block, no second SYRK; N = 97: three full
+    blocks plus one column; N = 449: the first step has 417 trailing rows,
+    more than one 384-row LDS chunk, so the off-diagonal chunk pair runs."""
+    _check_cholesky_batched(dev, B=49, N=N)
 
 
 def test_solves_match_torch(dev):
