@@ -72,6 +72,12 @@ def xinit(
 
 def _surrogate_eval(mdl: Model, x, optimize_mean_variance: bool):
     if optimize_mean_variance:
+        # device-resident [mean | round(var, 6)] block where the surrogate
+        # offers it (GPU fp32 GP): no host round trip per generation
+        if isinstance(x, torch.Tensor) and getattr(
+            mdl.objective, "supports_device_mean_variance", False
+        ):
+            return mdl.objective.evaluate_mean_variance_tensor(x)
         y_mean, y_var = mdl.objective.evaluate(_to_np(x))
         return np.column_stack((y_mean, np.round(y_var, 6)))
     # device-resident fast path: no numpy round trip per generation

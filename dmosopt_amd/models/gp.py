@@ -261,6 +261,68 @@ class _GPRBase:
             return mean, var
         return mean
 
+    def _native_pred_cache(self, device):
+        """(affine cache, per-fit predict args) for the fused native predict
+        calls. Raw queries: the per-dim normalization happens inside the
+        cross-kernel load (two fewer launches per generation). The static
+        per-fit args are cached once: the generation loop is host-dispatch-
+        bound, and re-checking contiguity/dtype of six unchanged tensors
+        every call costs ~8 us of host time."""
+        cache = getattr(self, "_affine_cache", None)
+        if cache is None or cache[0] != device:
+            lb = torch.as_tensor(self.xlb, dtype=torch.float32, device=device)
+            invrg = torch.as_tensor(
+                1.0 / self.xrg, dtype=torch.float32, device=device
+            )
+            self._affine_cache = cache = (device, lb, invrg)
+        f = self._fitted
+        pa = getattr(f, "_pred_args", None)
+        if pa is None:
+            pa = f._pred_args = (
+                f.X.contiguous(), f.theta.contiguous().float(),
+                f.alpha.contiguous().float(), f.y_mean.float(),
+                f.y_std.float(),
+                0.0 if (f.nu is None or f.nu == float("inf")) else float(f.nu),
+                bool(f.anisotropic),
+            )
+        return cache, pa
+
+    @property
+    def supports_device_mean_variance(self) -> bool:
+        """True when evaluate_mean_variance_tensor is available: the model
+        lives on the GPU in float32 with fp32 compute and the native
+        extension is in use."""
+        return bool(
+            self.device.type == "cuda"
+            and self.dtype == torch.float32
+            and self.compute == "fp32"
+            and not ops._FORCE_TORCH
+            and ops.native_available()
+        )
+
+    def evaluate_mean_variance_tensor(self, x: torch.Tensor) -> torch.Tensor:
+        """Device-resident mean-variance evaluate: (P, 2m) float32 laid out
+        [mean | round(var, 6)], no host trip. The variance is the fused
+        |Linv k*|^2 form (ops/hip/gp_variance.hip); the mean columns are
+        bitwise those of evaluate_tensor on a mean-only model."""
+        if not self.supports_device_mean_variance:
+            raise RuntimeError(
+                "evaluate_mean_variance_tensor needs a float32 GPU model with "
+                "fp32 compute and the native extension; use evaluate()"
+            )
+        from dmosopt_amd import _hipops
+
+        xr = x.to(self.device, torch.float32)
+        cache, pa = self._native_pred_cache(xr.device)
+        f = self._fitted
+        linv = getattr(f, "_pred_linv", None)
+        if linv is None:
+            linv = f._pred_linv = f.Linv.contiguous().float()
+        return _hipops.gp_predict_mean_var(
+            xr.contiguous(), pa[0], pa[1], pa[2], linv, pa[3], pa[4], pa[5],
+            pa[6], cache[1], cache[2], 6,
+        )
+
     def evaluate_tensor(self, x: torch.Tensor) -> torch.Tensor:
         """Device-resident evaluate: tensor in, tensor out, no host trip."""
         xr = x.to(self.device, self.dtype)
@@ -272,30 +334,9 @@ class _GPRBase:
             from dmosopt_amd import ops
 
             if ops.native_available():
-                # raw queries: the per-dim normalization happens inside the
-                # cross-kernel load (two fewer launches per generation)
-                cache = getattr(self, "_affine_cache", None)
-                if cache is None or cache[0] != xr.device:
-                    lb = torch.as_tensor(self.xlb, dtype=torch.float32, device=xr.device)
-                    invrg = torch.as_tensor(
-                        1.0 / self.xrg, dtype=torch.float32, device=xr.device
-                    )
-                    self._affine_cache = cache = (xr.device, lb, invrg)
                 from dmosopt_amd import _hipops
 
-                f = self._fitted
-                # static per-fit args cached once: the generation loop is
-                # host-dispatch-bound, and re-checking contiguity/dtype of
-                # six unchanged tensors every call costs ~8 us of host time
-                pa = getattr(f, "_pred_args", None)
-                if pa is None:
-                    pa = f._pred_args = (
-                        f.X.contiguous(), f.theta.contiguous().float(),
-                        f.alpha.contiguous().float(), f.y_mean.float(),
-                        f.y_std.float(),
-                        0.0 if (f.nu is None or f.nu == float("inf")) else float(f.nu),
-                        bool(f.anisotropic),
-                    )
+                cache, pa = self._native_pred_cache(xr.device)
                 return _hipops.gp_predict_mean(
                     xr.float().contiguous(), pa[0], pa[1], pa[2], pa[3],
                     pa[4], pa[5], pa[6], cache[1], cache[2],

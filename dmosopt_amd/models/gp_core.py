@@ -348,12 +348,49 @@ class FittedGP:
         Yn = (Y - y_mean[None, :]) / y_std[None, :]  # (N, m) standardized
         yb = Yn.T[:, :, None].contiguous()  # (m, N, 1)
         self.alpha = ops.chol_solve_batched(self.L, yb)  # (m, N, 1)
-        # On GPU, precompute K^-1 so per-generation posterior variance is a
-        # pair of batched GEMMs (rocBLAS/MFMA) instead of P triangular solves
-        self.Kinv: Optional[torch.Tensor] = None
-        if X.is_cuda:
-            eye = torch.eye(N, dtype=X.dtype, device=X.device)[None].expand(m, N, N).contiguous()
-            self.Kinv = ops.chol_solve_batched(self.L, eye)
+        # Kinv / Linv are built on the first variance request (properties
+        # below): the default mean-only mode never reads either, and each
+        # costs an N-right-hand-side solve per fit
+        self._Kinv: Optional[torch.Tensor] = None
+        self._Linv: Optional[torch.Tensor] = None
+
+    def _eye(self) -> torch.Tensor:
+        m, N = self.L.shape[0], self.L.shape[1]
+        return torch.eye(N, dtype=self.L.dtype, device=self.L.device)[None].expand(
+            m, N, N).contiguous()
+
+    @property
+    def Kinv(self) -> Optional[torch.Tensor]:
+        """K^-1 on GPU (None on CPU), for the torch variance path: the
+        quadratic term becomes a pair of batched GEMMs (rocBLAS/MFMA)
+        instead of P triangular solves. Built lazily, cached."""
+        if self._Kinv is None and self.X.is_cuda:
+            from dmosopt_amd import ops
+
+            self._Kinv = ops.chol_solve_batched(self.L, self._eye())
+        return self._Kinv
+
+    @property
+    def Linv(self) -> torch.Tensor:
+        """L^-1 (m, N, N), lower triangular, for the fused |Linv k*|^2
+        variance kernel. Built lazily by the forward solve, cached."""
+        if self._Linv is None:
+            from dmosopt_amd import ops
+
+            self._Linv = ops.tri_solve_forward(self.L, self._eye())
+        return self._Linv
+
+    def _fused_var_ok(self, Xq: torch.Tensor) -> bool:
+        from dmosopt_amd import ops
+
+        return (
+            self.compute == "fp32"
+            and Xq.is_cuda
+            and Xq.dtype == torch.float32
+            and self.X.dtype == torch.float32
+            and not ops._FORCE_TORCH
+            and ops.native_available()
+        )
 
     def predict(self, Xq: torch.Tensor, return_var: bool = True):
         """Posterior mean and variance at Xq (P, d) -> ((P, m), (P, m)).
@@ -372,6 +409,23 @@ class FittedGP:
             )
             if fused is not None:
                 return fused, None
+        if return_var and self._fused_var_ok(Xq):
+            from dmosopt_amd import ops
+
+            mv = ops.gp_predict_mean_var_fused(
+                Xq, self.X, self.theta, self.alpha, self.Linv, self.y_mean,
+                self.y_std, self.nu, self.anisotropic,
+            )
+            # The variance comes from the fused block. The mean keeps the
+            # bmm chain this method always had: evaluate() of a mean-only
+            # model comes through here too (the inner loop's initial
+            # population), and the gemv sums in another order — last-bit
+            # differences there change every later generation.
+            Ks = build_kernel(Xq, self.X, self.theta, nu=self.nu,
+                              anisotropic=self.anisotropic)
+            mean_n = torch.bmm(Ks, self.alpha)[:, :, 0]  # (m, P)
+            mean = self.y_mean[None, :] + self.y_std[None, :] * mean_n.T
+            return mean, mv[:, self.theta.shape[0]:]
         if self.compute == "bf16":
             from dmosopt_amd import ops
 

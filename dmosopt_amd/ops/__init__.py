@@ -262,6 +262,24 @@ def gp_predict_mean_fused(Xq, X, theta, alpha, y_mean, y_std, nu, anisotropic):
     return None
 
 
+def gp_predict_mean_var_fused(
+    Xq, X, theta, alpha, Linv, y_mean, y_std, nu, anisotropic,
+    q_lb=None, q_invrg=None, var_decimals=-1,
+):
+    """Fused posterior mean and variance, (P, 2B) laid out [mean | var] with
+    var = y_std^2 * max(sf2 + noise - |Linv k*|^2, 0); None when native
+    doesn't apply. ``var_decimals >= 0`` rounds the variance columns."""
+    if _use_native(Xq) and X.dtype == torch.float32:
+        nu_arg = 0.0 if (nu is None or nu == float("inf")) else float(nu)
+        return _native.gp_predict_mean_var(
+            Xq.to(torch.float32).contiguous(), X.contiguous(), theta.contiguous().float(),
+            alpha.contiguous().float(), Linv.contiguous().float(),
+            y_mean.float().contiguous(), y_std.float().contiguous(),
+            nu_arg, bool(anisotropic), q_lb, q_invrg, int(var_decimals),
+        )
+    return None
+
+
 def gp_nmll_fused(X, theta, y, nu, anisotropic, jitter):
     """Fused batched GP NMLL (assemble + Cholesky + solve + reduce) in one
     extension call; None if the native path does not apply."""

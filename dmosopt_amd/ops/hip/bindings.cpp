@@ -12,7 +12,9 @@
 
 extern "C" {
 void launch_matern_assemble_affine(const float*, const float*, const float*, float*, int, int, int, int, int, float, int, int, int, const float*, const float*, hipStream_t);
-void launch_gp_mean_gemv(const float*, const float*, const float*, const float*, float*, int, int, int, hipStream_t);
+void launch_gp_mean_gemv(const float*, const float*, const float*, const float*, float*, int, int, int, int, hipStream_t);
+int launch_gp_variance(const float*, const float*, const float*, const float*,
+                       float*, float*, int, int, int, int, float, hipStream_t);
 void launch_matern_assemble(const float*, const float*, const float*, float*,
                             int, int, int, int, int, float, int, int, int,
                             hipStream_t);
@@ -198,7 +200,115 @@ torch::Tensor gp_predict_mean(torch::Tensor Xq, torch::Tensor X,
   auto out = torch::empty({P, (long)B}, X.options());
   launch_gp_mean_gemv(Ks.data_ptr<float>(), alpha.data_ptr<float>(),
                       y_mean.data_ptr<float>(), y_std.data_ptr<float>(),
-                      out.data_ptr<float>(), B, P, N, cur_stream());
+                      out.data_ptr<float>(), B, P, N, B, cur_stream());
+  return out;
+}
+
+// Fused mean + variance predict (optimize_mean_variance mode): ONE cross-
+// kernel assembly feeds the mean gemv (the same kernel gp_predict_mean
+// launches, writing the left half of the (P, 2B) block, so the means are
+// bitwise those of gp_predict_mean) and the |Linv k*|^2 variance kernels
+// (gp_variance.hip), which write the right half. var_decimals >= 0 rounds
+// the variance columns to that many decimals in the epilogue.
+torch::Tensor gp_predict_mean_var(
+    torch::Tensor Xq, torch::Tensor X, torch::Tensor theta,
+    torch::Tensor alpha, torch::Tensor Linv, torch::Tensor y_mean,
+    torch::Tensor y_std, double nu, bool aniso,
+    c10::optional<torch::Tensor> q_lb = c10::nullopt,
+    c10::optional<torch::Tensor> q_invrg = c10::nullopt,
+    int64_t var_decimals = -1) {
+  CHECK_GPU(Xq);
+  CHECK_GPU(X);
+  CHECK_GPU(theta);
+  CHECK_GPU(alpha);
+  CHECK_GPU(Linv);
+  CHECK_GPU(y_mean);
+  CHECK_GPU(y_std);
+  TORCH_CHECK(Xq.dim() == 2 && X.dim() == 2 && theta.dim() == 2 &&
+                  Linv.dim() == 3,
+              "gp_predict_mean_var: Xq (P,D), X (N,D), theta (B,p), Linv "
+              "(B,N,N) required");
+  const int64_t P = Xq.size(0), N = X.size(0), D = X.size(1),
+                B = theta.size(0);
+  for (const auto& t : {Xq, X, theta, alpha, Linv, y_mean, y_std})
+    TORCH_CHECK(t.dtype() == torch::kFloat32,
+                "gp_predict_mean_var: float32 tensors required");
+  TORCH_CHECK(P >= 1 && N >= 1 && B >= 1 && D >= 1,
+              "gp_predict_mean_var: empty input");
+  TORCH_CHECK(Xq.size(1) == D, "gp_predict_mean_var: Xq/X width mismatch");
+  TORCH_CHECK(theta.size(1) == (aniso ? D + 2 : 3),
+              "gp_predict_mean_var: theta width does not match the kernel");
+  TORCH_CHECK(Linv.size(0) == B && Linv.size(1) == N && Linv.size(2) == N,
+              "gp_predict_mean_var: Linv must be (B,N,N)");
+  TORCH_CHECK(alpha.numel() == B * N && y_mean.numel() == B &&
+                  y_std.numel() == B,
+              "gp_predict_mean_var: alpha/y_mean/y_std shape mismatch");
+  if (q_lb || q_invrg) {
+    TORCH_CHECK(q_lb && q_invrg, "gp_predict_mean_var: q_lb and q_invrg "
+                                 "come together");
+    CHECK_GPU((*q_lb));
+    CHECK_GPU((*q_invrg));
+    TORCH_CHECK(q_lb->dtype() == torch::kFloat32 &&
+                    q_invrg->dtype() == torch::kFloat32 &&
+                    q_lb->numel() == D && q_invrg->numel() == D,
+                "gp_predict_mean_var: q_lb/q_invrg must be float32 (D,)");
+  }
+  // grid.z carries B and grid.y the tiles; the launch dims are ints
+  // grid.z carries B and grid.y the row / query tiles; the cross kernel
+  // indexes its inputs with ints and stages two 32 x (D|1) slabs in the
+  // default 64 KiB of LDS
+  TORCH_CHECK(B <= 65535 && (N + 31) / 32 <= 65535 &&
+                  (P + 31) / 32 <= 65535 && B * P < (1LL << 31) &&
+                  P * D < (1LL << 31) &&
+                  N * D < (1LL << 31) && D <= 254,
+              "gp_predict_mean_var: shape exceeds the launch bounds "
+              "(B <= 65535, N and P <= 2097120, D <= 254)");
+  TORCH_CHECK(var_decimals <= 9, "gp_predict_mean_var: var_decimals <= 9");
+  const int T = (int)((N + 31) / 32);
+  auto Ks = torch::empty({B, P, N}, X.options());
+  launch_matern_assemble_affine(
+      Xq.data_ptr<float>(), X.data_ptr<float>(), theta.data_ptr<float>(),
+      Ks.data_ptr<float>(), B, P, N, D, theta.size(1), 0.0f, nu_code(nu),
+      aniso ? 1 : 0, 0, q_lb ? q_lb->data_ptr<float>() : nullptr,
+      q_invrg ? q_invrg->data_ptr<float>() : nullptr, cur_stream());
+  hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "gp_predict_mean_var: cross-kernel launch "
+                                 "failed: ", hipGetErrorString(err));
+  auto out = torch::empty({P, 2 * B}, X.options());
+  launch_gp_mean_gemv(Ks.data_ptr<float>(), alpha.data_ptr<float>(),
+                      y_mean.data_ptr<float>(), y_std.data_ptr<float>(),
+                      out.data_ptr<float>(), B, P, N, 2 * B, cur_stream());
+  err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "gp_predict_mean_var: mean gemv launch "
+                                 "failed: ", hipGetErrorString(err));
+  // nu = 1/2 only: its kernel has an infinite slope in d2 at 0, so the
+  // ~1e-7 cancellation of the norms-form d2 costs ~7e-4 of variance at a
+  // query on a training point. The variance then reads a direct-difference
+  // cross kernel; the mean keeps the norms form (gp_predict_mean's bits).
+  torch::Tensor Kv = Ks;
+  if (nu_code(nu) == 1) {
+    Kv = torch::empty({B, P, N}, X.options());
+    launch_matern_assemble_affine(
+        Xq.data_ptr<float>(), X.data_ptr<float>(), theta.data_ptr<float>(),
+        Kv.data_ptr<float>(), B, P, N, D, theta.size(1), 0.0f, 1,
+        aniso ? 1 : 0, 2, q_lb ? q_lb->data_ptr<float>() : nullptr,
+        q_invrg ? q_invrg->data_ptr<float>() : nullptr, cur_stream());
+    err = hipGetLastError();
+    TORCH_CHECK(err == hipSuccess, "gp_predict_mean_var: direct cross-kernel "
+                                   "launch failed: ", hipGetErrorString(err));
+  }
+  auto part = torch::empty({B, (int64_t)T, P}, X.options());
+  float scale = 0.f;  // 0 = no rounding
+  if (var_decimals >= 0) {
+    scale = 1.f;
+    for (int64_t i = 0; i < var_decimals; ++i) scale *= 10.f;
+  }
+  const int rc = launch_gp_variance(
+      Linv.data_ptr<float>(), Kv.data_ptr<float>(), theta.data_ptr<float>(),
+      y_std.data_ptr<float>(), part.data_ptr<float>(), out.data_ptr<float>(),
+      B, P, N, theta.size(1), scale, cur_stream());
+  TORCH_CHECK(rc == 0, "gp_predict_mean_var: variance kernel launch failed: ",
+              hipGetErrorString((hipError_t)rc));
   return out;
 }
 
@@ -973,6 +1083,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("Xq"), py::arg("X"), py::arg("theta"), py::arg("alpha"),
         py::arg("y_mean"), py::arg("y_std"), py::arg("nu"), py::arg("aniso"),
         py::arg("q_lb") = py::none(), py::arg("q_invrg") = py::none());
+  m.def("gp_predict_mean_var", &gp_predict_mean_var,
+        "Fused cross-kernel + posterior mean + |Linv k*|^2 variance, (P, 2B)",
+        py::arg("Xq"), py::arg("X"), py::arg("theta"), py::arg("alpha"),
+        py::arg("Linv"), py::arg("y_mean"), py::arg("y_std"), py::arg("nu"),
+        py::arg("aniso"), py::arg("q_lb") = py::none(),
+        py::arg("q_invrg") = py::none(), py::arg("var_decimals") = -1);
   m.def("gp_nmll", &gp_nmll, "Fused batched GP NMLL (assemble+chol+solve+reduce)");
   m.def("cholesky_batched_", &cholesky_batched_,
         "In-place batched Cholesky; returns (logdet, info)");

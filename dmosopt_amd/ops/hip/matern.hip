@@ -36,7 +36,13 @@ __device__ __forceinline__ float matern_transform(float d2) {
 }
 
 // theta layout per batch row: [log sf2, log ell (1 or D), log noise]
-template <int NU, bool ANISO, bool SYMMETRIC>
+// DIRECT: exact (q-x)^2 accumulation instead of the norms+MFMA form. The
+// train kernel (SYMMETRIC) always uses it; a CROSS kernel may ask for it
+// (launch form 2) where the ~1e-7 cancellation in the norms-form d2 is too
+// much — the posterior VARIANCE under nu = 1/2, whose kernel has an
+// infinite slope in d2 at 0: a query on a training point gets r off by
+// sqrt(1e-7) ~ 3e-4 and the variance off by twice that.
+template <int NU, bool ANISO, bool SYMMETRIC, bool DIRECT = SYMMETRIC>
 __global__ void matern_assemble_kernel(
     const float* __restrict__ Xq,   // (P, D) query rows (== X when SYMMETRIC)
     const float* __restrict__ X,    // (N, D)
@@ -73,7 +79,7 @@ __global__ void matern_assemble_kernel(
   }
   __syncthreads();
 
-  if (SYMMETRIC) {
+  if (DIRECT) {
     // TRAIN kernel: exact (q-x)^2 accumulation. The norms+MFMA form
     // perturbs d2 by ~1e-6 (cancellation), which flips SCE-UA accept
     // decisions bit-wise and changes the fit's iteration count — the
@@ -98,7 +104,7 @@ __global__ void matern_assemble_kernel(
           d2 = fmaf(t, t, d2);
         }
         float v = sf2 * matern_transform<NU>(d2);
-        if (gp == gn) v += noise + jitter;
+        if (SYMMETRIC && gp == gn) v += noise + jitter;
         K[((long long)b * P + gp) * N + gn] = v;
       }
     }
@@ -158,8 +164,15 @@ extern "C" void launch_matern_assemble_affine(
     hipLaunchKernelGGL((matern_assemble_kernel<NU, AN, SY>), grid, block,   \
                        lds_bytes, stream, Xq, X, theta, K, P, N, D,         \
                        theta_stride, jitter, q_lb, q_invrg)
+  // symmetric: 0 = cross (norms+MFMA), 1 = train, 2 = cross, direct form
+  #define DISPATCH_DIRECT(NU, AN)                                           \
+    hipLaunchKernelGGL((matern_assemble_kernel<NU, AN, false, true>), grid, \
+                       block, lds_bytes, stream, Xq, X, theta, K, P, N, D,  \
+                       theta_stride, jitter, q_lb, q_invrg)
   #define DISPATCH_AN(NU)                                                   \
-    if (aniso) {                                                            \
+    if (symmetric == 2) {                                                   \
+      if (aniso) DISPATCH_DIRECT(NU, true); else DISPATCH_DIRECT(NU, false); \
+    } else if (aniso) {                                                     \
       if (symmetric) DISPATCH(NU, true, true); else DISPATCH(NU, true, false); \
     } else {                                                                \
       if (symmetric) DISPATCH(NU, false, true); else DISPATCH(NU, false, false); \
@@ -171,6 +184,7 @@ extern "C" void launch_matern_assemble_affine(
     default: DISPATCH_AN(5); break;
   }
   #undef DISPATCH_AN
+  #undef DISPATCH_DIRECT
   #undef DISPATCH
 }
 
@@ -189,13 +203,16 @@ extern "C" void launch_matern_assemble(
 // deterministic), writing the CONTIGUOUS (P, B) result directly —
 // replaces at::bmm + addcmul + transpose-contiguous (3 dispatches and
 // ~30 us of host time per generation; the GEMM itself is overkill for a
-// (B,P,N)x(B,N,1) matvec).
+// (B,P,N)x(B,N,1) matvec). ldo is the output row stride: B for the
+// mean-only result, 2B when the means are the left half of the (P, 2B)
+// mean|variance block — the SAME kernel serves both so the means are
+// bitwise identical.
 __global__ void gp_mean_gemv_kernel(const float* __restrict__ Ks,
                                     const float* __restrict__ alpha,
                                     const float* __restrict__ y_mean,
                                     const float* __restrict__ y_std,
                                     float* __restrict__ out, int B, int P,
-                                    int N) {
+                                    int N, int ldo) {
   const long long w =
       ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;  // wave id
   const int lane = threadIdx.x & 63;
@@ -206,16 +223,16 @@ __global__ void gp_mean_gemv_kernel(const float* __restrict__ Ks,
   float acc = 0.f;
   for (int n = lane; n < N; n += 64) acc = fmaf(row[n], al[n], acc);
   for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-  if (lane == 0) out[(long long)p * B + b] = fmaf(y_std[b], acc, y_mean[b]);
+  if (lane == 0) out[(long long)p * ldo + b] = fmaf(y_std[b], acc, y_mean[b]);
 }
 
 extern "C" void launch_gp_mean_gemv(const float* Ks, const float* alpha,
                                     const float* y_mean, const float* y_std,
                                     float* out, int B, int P, int N,
-                                    hipStream_t stream) {
+                                    int ldo, hipStream_t stream) {
   const long long waves = (long long)B * P;
   const long long threads = waves * 64;
   hipLaunchKernelGGL(gp_mean_gemv_kernel, dim3((int)((threads + 255) / 256)),
                      dim3(256), 0, stream, Ks, alpha, y_mean, y_std, out, B,
-                     P, N);
+                     P, N, ldo);
 }

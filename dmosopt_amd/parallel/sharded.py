@@ -56,6 +56,22 @@ class ShardedObjective:
         full = ctx.all_gather_interleaved(m.to(torch.float32).contiguous(), P)
         return full.to(dtype=x.dtype, device=x.device)
 
+    def evaluate_mean_variance_tensor(self, x: torch.Tensor) -> torch.Tensor:
+        """Mean-variance mode on the device route: each rank evaluates its
+        strided shard with the inner fused call and ONE all_gather moves the
+        (P_shard, 2m) float32 [mean | var] block. A query's fused result
+        does not depend on its batch, so the reassembled tensor equals the
+        full-batch one bitwise. Offered only when the inner surrogate
+        reports ``supports_device_mean_variance`` (delegated attribute)."""
+        ctx = self._ctx
+        P = int(x.shape[0])
+        pad = (ctx.world - P % ctx.world) % ctx.world
+        xp = torch.cat([x, x[-1:].expand(pad, -1)], dim=0) if pad else x
+        shard = xp[ctx.rank :: ctx.world]
+        mv = self._inner.evaluate_mean_variance_tensor(shard)
+        full = ctx.all_gather_interleaved(mv.to(torch.float32).contiguous(), P)
+        return full.to(device=x.device)
+
     # ---------------------------------------------------------------- numpy
     def evaluate(self, x):
         ctx = self._ctx
