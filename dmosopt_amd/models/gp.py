@@ -23,7 +23,12 @@ import numpy as np
 import torch
 
 from dmosopt_amd import ops
-from dmosopt_amd.models.gp_core import FittedGP, _nmll_bind_enabled, batched_nmll
+from dmosopt_amd.models.gp_core import (
+    FittedGP,
+    _nmll_bind_enabled,
+    batched_nmll,
+    batched_nmll_and_grad,
+)
 from dmosopt_amd.models.sceua import sceua_batched
 
 
@@ -63,6 +68,9 @@ class _GPRBase:
         top_k=None,
         adam_lr=0.08,
         adam_iters=150,
+        grad_restarts=8,
+        grad_iters=200,
+        grad_lr=0.5,
         batch_size=None,
         device=None,
         dtype=None,
@@ -177,6 +185,10 @@ class _GPRBase:
             theta = torch.as_tensor(bestx, dtype=self.dtype, device=self.device)
         elif optimizer == "adam":
             theta = self._fit_adam(X, Yn, bl, bu, nopt, m, adam_lr, adam_iters, seed)
+        elif optimizer == "grad":
+            theta = self._fit_grad(
+                X, Yn, bl, bu, m, grad_restarts, grad_iters, grad_lr, seed
+            )
         else:
             raise ValueError(f"Unknown GP optimizer {optimizer!r}")
 
@@ -228,6 +240,85 @@ class _GPRBase:
                 theta.clamp_(bl_t, bu_t)
                 theta.nan_to_num_(nan=0.0)
         return best_theta
+
+    def _adam_init(self, bl_t, bu_t, m):
+        """_fit_adam's initial point (sf2=1, ell=0.5, noise=1e-6), (m, p)."""
+        init = 0.5 * (bl_t + bu_t)[None, :].repeat(m, 1)
+        init[:, 0] = 0.0
+        init[:, 1:-1] = math.log(0.5)
+        init[:, -1] = math.log(1e-6)
+        return init
+
+    def _grad_starts(self, bl, bu, m, restarts, seed):
+        """(restarts, m, p) start points of the multi-start gradient fit:
+        start 0 is _fit_adam's initial point clipped to the box, the others
+        are uniform in the box from a CPU generator seeded with ``seed``
+        (drawn in float64 on the host, so CPU and GPU fits of one seed start
+        from the same points)."""
+        g = torch.Generator(device="cpu")
+        if seed is not None:
+            g.manual_seed(int(seed))
+        bl64 = torch.as_tensor(bl, dtype=torch.float64)
+        bu64 = torch.as_tensor(bu, dtype=torch.float64)
+        starts = torch.empty(restarts, m, bl64.numel(), dtype=torch.float64)
+        starts[0] = torch.minimum(
+            torch.maximum(self._adam_init(bl64, bu64, m), bl64), bu64
+        )
+        if restarts > 1:
+            u = torch.rand(restarts - 1, m, bl64.numel(), generator=g,
+                           dtype=torch.float64)
+            starts[1:] = bl64 + u * (bu64 - bl64)
+        return starts.to(device=self.device, dtype=self.dtype)
+
+    def _fit_grad(self, X, Yn, bl, bu, m, restarts, iters, lr, seed):
+        """Multi-start projected Adam on the analytic NMLL gradient.
+
+        All restarts x m candidates advance together: one
+        batched_nmll_and_grad call (on the GPU one fused extension call:
+        assemble, Cholesky, solves, gradient kernels) per iteration, then an
+        Adam step in log space clamped to the SCE-UA box [bl, bu], with the
+        learning rate on a cosine from ``lr`` to 0 over ``iters``. The best
+        finite NMLL of every candidate over all iterations is tracked on the
+        device (no host sync inside the loop); the result for an objective is
+        its best candidate over the restarts. The search evaluates the same
+        NMLL as the SCE-UA search (same jitter), so the two are comparable."""
+        restarts, iters = int(restarts), int(iters)
+        if restarts < 1 or iters < 0:
+            raise ValueError("grad_restarts must be >= 1 and grad_iters >= 0")
+        bl_t = torch.as_tensor(bl, dtype=self.dtype, device=self.device)
+        bu_t = torch.as_tensor(bu, dtype=self.dtype, device=self.device)
+        p = bl_t.numel()
+        theta = self._grad_starts(bl, bu, m, restarts, seed).reshape(restarts * m, p)
+        theta = torch.minimum(torch.maximum(theta, bl_t), bu_t)
+        y_rows = Yn.T.contiguous().repeat(restarts, 1)  # row r*m+s -> objective s
+        best_theta = theta.clone()
+        best_f = torch.full((restarts * m,), float("inf"), dtype=self.dtype,
+                            device=self.device)
+        m1 = torch.zeros_like(theta)
+        m2 = torch.zeros_like(theta)
+        beta1, beta2, eps = 0.9, 0.999, 1e-8
+        for t in range(iters + 1):
+            f, g = batched_nmll_and_grad(
+                X, y_rows, theta, nu=self.nu, anisotropic=self.anisotropic
+            )
+            better = torch.isfinite(f) & (f < best_f)
+            best_f = torch.where(better, f, best_f)
+            best_theta = torch.where(better[:, None], theta, best_theta)
+            if t == iters:
+                break
+            g = torch.where(torch.isfinite(g), g, torch.zeros_like(g))
+            m1 = beta1 * m1 + (1.0 - beta1) * g
+            m2 = beta2 * m2 + (1.0 - beta2) * g * g
+            step = 0.5 * lr * (1.0 + math.cos(math.pi * t / iters))
+            upd = (m1 / (1.0 - beta1 ** (t + 1))) / (
+                torch.sqrt(m2 / (1.0 - beta2 ** (t + 1))) + eps
+            )
+            theta = torch.minimum(torch.maximum(theta - step * upd, bl_t), bu_t)
+        pick = torch.argmin(best_f.view(restarts, m), dim=0)  # (m,)
+        cols = torch.arange(m, device=self.device)
+        #: best NMLL found per objective (device tensor, search jitter)
+        self.fit_nmll = best_f.view(restarts, m)[pick, cols]
+        return best_theta.view(restarts, m, p)[pick, cols].contiguous()
 
     # ---------------------------------------------------------------- API
     def predict(self, xin):

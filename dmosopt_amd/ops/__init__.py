@@ -292,6 +292,21 @@ def gp_nmll_fused(X, theta, y, nu, anisotropic, jitter):
     return None
 
 
+def gp_nmll_grad(X, theta, y, nu, anisotropic, jitter):
+    """Batched GP NMLL and its analytic gradient -> (nmll (B,), grad (B,p)).
+    Float32 GPU tensors run the fused native pipeline (value pipeline of
+    gp_nmll, then alpha, K^-1 and the gp_nmll_grad.hip tile kernels in the
+    same extension call); everything else the closed form in plain torch."""
+    if _use_native(X) and X.dtype == torch.float32:
+        nu_arg = 0.0 if (nu is None or nu == float("inf")) else float(nu)
+        nmll, grad = _native.gp_nmll_grad(
+            X.contiguous(), theta.contiguous().float(), y.contiguous().float(),
+            nu_arg, bool(anisotropic), float(jitter),
+        )
+        return nmll, grad
+    return torch_ref.gp_nmll_grad_ref(X, theta, y, nu, anisotropic, jitter)
+
+
 def matern_train_kernel(X, theta, nu, anisotropic, jitter):
     """Batched symmetric kernel matrices K (B,N,N) with noise+jitter diag."""
     if _use_native(X) and X.dtype == torch.float32:

@@ -13,6 +13,11 @@
 extern "C" {
 void launch_matern_assemble_affine(const float*, const float*, const float*, float*, int, int, int, int, int, float, int, int, int, const float*, const float*, hipStream_t);
 void launch_gp_mean_gemv(const float*, const float*, const float*, const float*, float*, int, int, int, int, hipStream_t);
+int launch_gp_fill_identity(float*, int, int, hipStream_t);
+int gp_nmll_grad_tiles(int);
+int launch_gp_nmll_grad(const float*, const float*, const float*, const float*,
+                        const float*, const int*, float*, float*, int, int,
+                        int, int, int, int, hipStream_t);
 int launch_gp_variance(const float*, const float*, const float*, const float*,
                        float*, float*, int, int, int, int, float, hipStream_t);
 void launch_matern_assemble(const float*, const float*, const float*, float*,
@@ -173,6 +178,97 @@ torch::Tensor gp_nmll(torch::Tensor X, torch::Tensor theta, torch::Tensor y,
                      info.data_ptr<int>(), out.data_ptr<float>(), B, N, c,
                      cur_stream());
   return out;
+}
+
+// Fused NMLL value AND analytic gradient for a batch of theta. The value
+// pipeline is gp_nmll's, launch for launch (same kernels, same order, same
+// fallback branch), so nmll is bitwise what gp_nmll returns; the gradient
+// stages follow it on the same stream: backward solve for alpha, K^-1 by the
+// forward and backward solves on an identity right-hand side, then the tile
+// kernels of gp_nmll_grad.hip. Returns {nmll (B,), grad (B,p)}; a candidate
+// whose factorization failed gets +inf and a zero gradient row.
+std::vector<torch::Tensor> gp_nmll_grad(torch::Tensor X, torch::Tensor theta,
+                                        torch::Tensor y, double nu,
+                                        bool aniso, double jitter) {
+  CHECK_GPU(X);
+  CHECK_GPU(theta);
+  CHECK_GPU(y);
+  TORCH_CHECK(X.dim() == 2 && theta.dim() == 2,
+              "gp_nmll_grad: X (N,D) and theta (B,p) required");
+  for (const auto& t : {X, theta, y})
+    TORCH_CHECK(t.dtype() == torch::kFloat32,
+                "gp_nmll_grad: float32 tensors required");
+  const int64_t N = X.size(0), D = X.size(1), B = theta.size(0),
+                p = theta.size(1);
+  TORCH_CHECK(N >= 1 && B >= 1 && D >= 1, "gp_nmll_grad: empty input");
+  TORCH_CHECK(p == (aniso ? D + 2 : 3),
+              "gp_nmll_grad: theta width does not match the kernel");
+  TORCH_CHECK((y.dim() == 1 && y.size(0) == N) ||
+                  (y.dim() == 2 && y.size(0) == B && y.size(1) == N),
+              "gp_nmll_grad: y must be (N,) or (B,N)");
+  // grid.y / grid.x carry B in the gradient, assemble and solve launches and
+  // grid.y the N right-hand sides of the K^-1 solves; the slabs of a tile
+  // pair (2 x 32 x (D|1) floats) stay inside the default 64 KiB of LDS
+  TORCH_CHECK(B <= 65535 && N <= 65535 && D <= 128,
+              "gp_nmll_grad: shape exceeds the launch bounds (B, N <= 65535, "
+              "D <= 128)");
+  auto stream = cur_stream();
+  auto K = torch::empty({B, N, N}, X.options());
+  launch_matern_assemble(X.data_ptr<float>(), X.data_ptr<float>(),
+                         theta.data_ptr<float>(), K.data_ptr<float>(), B, N, N,
+                         D, p, (float)jitter, nu_code(nu), aniso ? 1 : 0, 1,
+                         stream);
+  hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "gp_nmll_grad: assemble launch failed: ",
+              hipGetErrorString(err));
+  auto logdet = torch::empty({B}, X.options());
+  auto info = torch::zeros({B}, X.options().dtype(torch::kInt32));
+  torch::Tensor Z = (y.dim() == 1)
+                        ? y.unsqueeze(0).expand({B, N}).contiguous()
+                        : y.contiguous().clone();
+  Z = Z.view({B, N, 1});
+  if (launch_cholesky_fused_solve(K.data_ptr<float>(),
+                                  logdet.data_ptr<float>(),
+                                  info.data_ptr<int>(), Z.data_ptr<float>(),
+                                  B, N, stream) != 0) {
+    launch_cholesky_batched(K.data_ptr<float>(), logdet.data_ptr<float>(),
+                            info.data_ptr<int>(), B, N, stream);
+    launch_forward_solve_batched(K.data_ptr<float>(), Z.data_ptr<float>(), B,
+                                 N, 1, stream);
+  }
+  auto out = torch::empty({B}, X.options());
+  const float c = 0.5f * (float)N * 1.8378770664093453f;  // log(2*pi)
+  launch_nmll_reduce(Z.data_ptr<float>(), logdet.data_ptr<float>(),
+                     info.data_ptr<int>(), out.data_ptr<float>(), B, N, c,
+                     stream);
+  err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "gp_nmll_grad: NMLL pipeline launch failed: ",
+              hipGetErrorString(err));
+  // alpha = L^-T z, in place (the reduce above has read z)
+  launch_backward_solve_batched(K.data_ptr<float>(), Z.data_ptr<float>(), B,
+                                N, 1, stream);
+  auto Kinv = torch::empty({B, N, N}, X.options());
+  int rc = launch_gp_fill_identity(Kinv.data_ptr<float>(), B, N, stream);
+  TORCH_CHECK(rc == 0, "gp_nmll_grad: identity fill launch failed: ",
+              hipGetErrorString((hipError_t)rc));
+  launch_forward_solve_batched(K.data_ptr<float>(), Kinv.data_ptr<float>(), B,
+                               N, N, stream);
+  launch_backward_solve_batched(K.data_ptr<float>(), Kinv.data_ptr<float>(),
+                                B, N, N, stream);
+  err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "gp_nmll_grad: solve launch failed: ",
+              hipGetErrorString(err));
+  auto part = torch::empty({B, (int64_t)gp_nmll_grad_tiles((int)N), p},
+                           X.options());
+  auto grad = torch::empty({B, p}, X.options());
+  rc = launch_gp_nmll_grad(
+      X.data_ptr<float>(), theta.data_ptr<float>(), Kinv.data_ptr<float>(),
+      Z.data_ptr<float>(), out.data_ptr<float>(), info.data_ptr<int>(),
+      part.data_ptr<float>(), grad.data_ptr<float>(), B, N, D, p, nu_code(nu),
+      aniso ? 1 : 0, stream);
+  TORCH_CHECK(rc == 0, "gp_nmll_grad: gradient kernel launch failed: ",
+              hipGetErrorString((hipError_t)rc));
+  return {out, grad};
 }
 
 // Fused posterior-mean predict for the inner-MOEA surrogate evaluate:
@@ -1090,6 +1186,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("aniso"), py::arg("q_lb") = py::none(),
         py::arg("q_invrg") = py::none(), py::arg("var_decimals") = -1);
   m.def("gp_nmll", &gp_nmll, "Fused batched GP NMLL (assemble+chol+solve+reduce)");
+  m.def("gp_nmll_grad", &gp_nmll_grad,
+        "Fused batched GP NMLL value and analytic gradient");
   m.def("cholesky_batched_", &cholesky_batched_,
         "In-place batched Cholesky; returns (logdet, info)");
   m.def("cholesky_multik_sched_", &cholesky_multik_sched_,

@@ -334,3 +334,92 @@ def filter_samples(y: Tensor, *companions, nan: str = "remove", outliers: str = 
     for c in companions:
         out.append(c[mask] if c is not None else None)
     return tuple(out)
+
+
+# -------------------------------------------------------------------- GP ops
+def gp_nmll_grad_ref(X: Tensor, theta: Tensor, y: Tensor, nu, anisotropic: bool,
+                     jitter: float) -> Tuple[Tensor, Tensor]:
+    """GP negative log marginal likelihood and its analytic gradient for a
+    batch of theta, in the input dtype.
+
+    X (N, D); theta (B, p) = [log sf2, log ell (1 or D), log noise]; y (N,)
+    shared or (B, N) per-candidate rows. K = sf2 C + (noise + jitter) I,
+    alpha = K^-1 y, W = K^-1 - alpha alpha^T, u_k = ((x_ik - x_jk)/ell_k)^2,
+    d2 = sum_k u_k, g = -dc/d(d2):
+
+        d/d log sf2   = 1/2 sf2   sum_ij W_ij c_ij
+        d/d log noise = 1/2 noise tr(W)
+        d/d log ell_k =     sf2   sum_ij W_ij g_ij u_k,ij   (isotropic: d2)
+
+    d2 is the direct-difference sum, one dimension at a time (no (B,N,N,D)
+    temporary). Returns (nmll (B,), grad (B, p)); a failed factorization or
+    a non-finite value gives +inf and a zero gradient row.
+    """
+    import math
+
+    N, D = X.shape
+    B = theta.shape[0]
+    theta = theta.to(X.dtype)
+    sf2 = torch.exp(theta[:, 0])
+    noise = torch.exp(theta[:, -1])
+    inv_ell = torch.exp(-theta[:, 1 : 1 + D]) if anisotropic else torch.exp(-theta[:, 1:2])
+    xs = X[None, :, :] * inv_ell[:, None, :]  # (B, N, D)
+
+    def u_k(k):
+        t = xs[:, :, None, k] - xs[:, None, :, k]
+        return t * t
+
+    d2 = torch.zeros(B, N, N, dtype=X.dtype, device=X.device)
+    for k in range(D):
+        d2 += u_k(k)
+    rbf = nu is None or nu == float("inf") or nu == 0.0
+    if rbf:
+        c = torch.exp(-0.5 * d2)
+        g = 0.5 * c
+    else:
+        r = torch.sqrt(d2)
+        if nu == 0.5:
+            c = torch.exp(-r)
+            pos = r > 0
+            g = torch.where(pos, c / (2.0 * torch.where(pos, r, torch.ones_like(r))),
+                            torch.zeros_like(r))
+        elif nu == 1.5:
+            s = math.sqrt(3.0) * r
+            e = torch.exp(-s)
+            c = (1.0 + s) * e
+            g = 1.5 * e
+        elif nu == 2.5:
+            s = math.sqrt(5.0) * r
+            e = torch.exp(-s)
+            c = (1.0 + s + (5.0 / 3.0) * d2) * e
+            g = (5.0 / 6.0) * (1.0 + s) * e
+        else:
+            raise ValueError(f"Unsupported Matern nu={nu}")
+    eye = torch.eye(N, dtype=X.dtype, device=X.device)
+    K = sf2[:, None, None] * c + (noise + jitter)[:, None, None] * eye
+    L, info = torch.linalg.cholesky_ex(K)
+    bad = info != 0
+    # keep the solves finite for a failed candidate; its row is masked below
+    L = torch.where(bad[:, None, None], eye, L)
+    yb = (y[None, :].expand(B, N) if y.dim() == 1 else y).to(X.dtype)
+    alpha = torch.cholesky_solve(yb[:, :, None], L)[:, :, 0]  # (B, N)
+    Kinv = torch.cholesky_solve(eye[None].expand(B, N, N), L)
+    W = Kinv - alpha[:, :, None] * alpha[:, None, :]
+    nmll = (
+        0.5 * (yb * alpha).sum(dim=1)
+        + torch.log(torch.diagonal(L, dim1=-2, dim2=-1)).sum(dim=-1)
+        + 0.5 * N * math.log(2.0 * math.pi)
+    )
+    grad = torch.empty_like(theta)
+    grad[:, 0] = 0.5 * sf2 * (W * c).sum(dim=(1, 2))
+    grad[:, -1] = 0.5 * noise * torch.diagonal(W, dim1=-2, dim2=-1).sum(dim=-1)
+    H = W * g
+    if anisotropic:
+        for k in range(D):
+            grad[:, 1 + k] = sf2 * (H * u_k(k)).sum(dim=(1, 2))
+    else:
+        grad[:, 1] = sf2 * (H * d2).sum(dim=(1, 2))
+    bad = bad | ~torch.isfinite(nmll)
+    nmll = torch.where(bad, torch.full_like(nmll, float("inf")), nmll)
+    grad = torch.where(bad[:, None], torch.zeros_like(grad), grad)
+    return nmll, grad

@@ -34,6 +34,7 @@ ext = CUDAExtension(
         os.path.join("dmosopt_amd", "ops", "hip", "matern_bf16.hip"),
         os.path.join("dmosopt_amd", "ops", "hip", "agemoea_survival.hip"),
         os.path.join("dmosopt_amd", "ops", "hip", "gp_variance.hip"),
+        os.path.join("dmosopt_amd", "ops", "hip", "gp_nmll_grad.hip"),
     ],
     include_dirs=[HIP_DIR],
     extra_compile_args={
