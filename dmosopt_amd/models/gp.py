@@ -205,11 +205,7 @@ class _GPRBase:
             g.manual_seed(int(seed))
         bl_t = torch.as_tensor(bl, dtype=self.dtype, device=self.device)
         bu_t = torch.as_tensor(bu, dtype=self.dtype, device=self.device)
-        init = 0.5 * (bl_t + bu_t)[None, :].repeat(m, 1)
-        # sensible inits: sf2=1, ell=0.5, noise=1e-6 (reference defaults)
-        init[:, 0] = 0.0
-        init[:, 1:-1] = math.log(0.5)
-        init[:, -1] = math.log(1e-6)
+        init = self._adam_init(bl_t, bu_t, m)
         theta = init.clone().requires_grad_(True)
         opt = torch.optim.Adam([theta], lr=lr)
         best_theta = init.clone()
@@ -242,7 +238,8 @@ class _GPRBase:
         return best_theta
 
     def _adam_init(self, bl_t, bu_t, m):
-        """_fit_adam's initial point (sf2=1, ell=0.5, noise=1e-6), (m, p)."""
+        """_fit_adam's initial point (sf2=1, ell=0.5, noise=1e-6: the
+        reference defaults), (m, p)."""
         init = 0.5 * (bl_t + bu_t)[None, :].repeat(m, 1)
         init[:, 0] = 0.0
         init[:, 1:-1] = math.log(0.5)
@@ -369,27 +366,16 @@ class _GPRBase:
         f = self._fitted
         pa = getattr(f, "_pred_args", None)
         if pa is None:
-            pa = f._pred_args = (
-                f.X.contiguous(), f.theta.contiguous().float(),
-                f.alpha.contiguous().float(), f.y_mean.float(),
-                f.y_std.float(),
-                0.0 if (f.nu is None or f.nu == float("inf")) else float(f.nu),
-                bool(f.anisotropic),
+            pa = f._pred_args = ops.gp_pred_args(
+                f.X, f.theta, f.alpha, f.y_mean, f.y_std, f.nu, f.anisotropic
             )
         return cache, pa
 
     @property
     def supports_device_mean_variance(self) -> bool:
-        """True when evaluate_mean_variance_tensor is available: the model
-        lives on the GPU in float32 with fp32 compute and the native
-        extension is in use."""
-        return bool(
-            self.device.type == "cuda"
-            and self.dtype == torch.float32
-            and self.compute == "fp32"
-            and not ops._FORCE_TORCH
-            and ops.native_available()
-        )
+        """True when evaluate_mean_variance_tensor is available: a float32
+        GPU model with fp32 compute on the native path."""
+        return self.compute == "fp32" and ops.native_fp32(self._fitted.X)
 
     def evaluate_mean_variance_tensor(self, x: torch.Tensor) -> torch.Tensor:
         """Device-resident mean-variance evaluate: (P, 2m) float32 laid out
@@ -401,17 +387,14 @@ class _GPRBase:
                 "evaluate_mean_variance_tensor needs a float32 GPU model with "
                 "fp32 compute and the native extension; use evaluate()"
             )
-        from dmosopt_amd import _hipops
-
         xr = x.to(self.device, torch.float32)
         cache, pa = self._native_pred_cache(xr.device)
         f = self._fitted
         linv = getattr(f, "_pred_linv", None)
         if linv is None:
             linv = f._pred_linv = f.Linv.contiguous().float()
-        return _hipops.gp_predict_mean_var(
-            xr.contiguous(), pa[0], pa[1], pa[2], linv, pa[3], pa[4], pa[5],
-            pa[6], cache[1], cache[2], 6,
+        return ops.gp_predict_mean_var_cached(
+            xr.contiguous(), pa, linv, cache[1], cache[2], 6
         )
 
     def evaluate_tensor(self, x: torch.Tensor) -> torch.Tensor:
@@ -419,19 +402,13 @@ class _GPRBase:
         xr = x.to(self.device, self.dtype)
         if (
             not self.return_mean_variance
-            and xr.device.type == "cuda"
             and self.compute != "bf16"
+            and ops.native_fp32(self._fitted.X)
         ):
-            from dmosopt_amd import ops
-
-            if ops.native_available():
-                from dmosopt_amd import _hipops
-
-                cache, pa = self._native_pred_cache(xr.device)
-                return _hipops.gp_predict_mean(
-                    xr.float().contiguous(), pa[0], pa[1], pa[2], pa[3],
-                    pa[4], pa[5], pa[6], cache[1], cache[2],
-                )
+            cache, pa = self._native_pred_cache(xr.device)
+            return ops.gp_predict_mean_cached(
+                xr.contiguous(), pa, cache[1], cache[2]
+            )
         xq = self.normalize_query(xr)
         mean, _ = self._fitted.predict(xq, return_var=self.return_mean_variance)
         return mean

@@ -22,6 +22,8 @@ from typing import Optional, Tuple
 
 import torch
 
+from dmosopt_amd import ops
+
 
 def _strict_cpu_det() -> bool:
     import os
@@ -133,8 +135,6 @@ def build_kernel(
 ) -> torch.Tensor:
     """Dispatching kernel build: gfx950 fused-assembly kernel on GPU,
     torch on CPU."""
-    from dmosopt_amd import ops
-
     if X2 is None:
         return ops.matern_train_kernel(X1, theta, nu, anisotropic, jitter)
     return ops.matern_cross_kernel(X1, X2, theta, nu, anisotropic)
@@ -155,8 +155,6 @@ class _NmllGraph:
     (_bind), theta on every call."""
 
     def __init__(self, X, y, theta, nu, anisotropic, jitter):
-        from dmosopt_amd import ops
-
         self.Xb = X.contiguous().clone()
         self.yb = y.contiguous().clone()
         self.tb = theta.contiguous().clone()
@@ -254,14 +252,7 @@ def batched_nmll(
             quad = (yb * alpha).sum(dim=(1, 2))
             logdet = 2.0 * torch.log(torch.diagonal(L, dim1=-2, dim2=-1)).sum(dim=-1)
         else:
-            from dmosopt_amd import ops
-
-            if (
-                X.is_cuda
-                and X.dtype == torch.float32
-                and ops.native_available()
-                and _nmll_graph_enabled()
-            ):
+            if ops.native_fp32(X) and _nmll_graph_enabled():
                 key = (
                     B, N, X.shape[1], theta.shape[1], y.dim(), nu, anisotropic,
                     float(jitter),
@@ -311,8 +302,6 @@ def batched_nmll_and_grad(
     fused ``gp_nmll``; everything else runs ``torch_ref.gp_nmll_grad_ref``
     in the input dtype.
     """
-    from dmosopt_amd import ops
-
     with _single_threaded_cpu_math(not X.is_cuda):
         return ops.gp_nmll_grad(X, theta, y, nu, anisotropic, jitter)
 
@@ -345,15 +334,13 @@ class FittedGP:
         # predictions use the bf16 cross kernel (BASELINE config #2); the
         # SCE-UA fit that produced theta is always fp32 (bit-stability)
         self.compute = compute if X.is_cuda else "fp32"
-        from dmosopt_amd import ops
-
         m, N = theta.shape[0], X.shape[0]
         with _single_threaded_cpu_math(not X.is_cuda):
             self._build_posterior(X, Y, theta, y_mean, y_std, nu, anisotropic,
-                                  jitter, ops, m, N)
+                                  jitter, m, N)
 
     def _build_posterior(self, X, Y, theta, y_mean, y_std, nu, anisotropic,
-                         jitter, ops, m, N):
+                         jitter, m, N):
         K = build_kernel(X, None, theta, nu=nu, anisotropic=anisotropic, jitter=jitter)
         if self.compute == "bf16":
             self.L, _, info = ops.chol_factor_batched_bf16(K)
@@ -391,8 +378,6 @@ class FittedGP:
         quadratic term becomes a pair of batched GEMMs (rocBLAS/MFMA)
         instead of P triangular solves. Built lazily, cached."""
         if self._Kinv is None and self.X.is_cuda:
-            from dmosopt_amd import ops
-
             self._Kinv = ops.chol_solve_batched(self.L, self._eye())
         return self._Kinv
 
@@ -401,22 +386,12 @@ class FittedGP:
         """L^-1 (m, N, N), lower triangular, for the fused |Linv k*|^2
         variance kernel. Built lazily by the forward solve, cached."""
         if self._Linv is None:
-            from dmosopt_amd import ops
-
             self._Linv = ops.tri_solve_forward(self.L, self._eye())
         return self._Linv
 
-    def _fused_var_ok(self, Xq: torch.Tensor) -> bool:
-        from dmosopt_amd import ops
-
-        return (
-            self.compute == "fp32"
-            and Xq.is_cuda
-            and Xq.dtype == torch.float32
-            and self.X.dtype == torch.float32
-            and not ops._FORCE_TORCH
-            and ops.native_available()
-        )
+    def _destandardize(self, mean_n: torch.Tensor) -> torch.Tensor:
+        """Standardized (m, P) posterior mean -> (P, m) in the units of Y."""
+        return self.y_mean[None, :] + self.y_std[None, :] * mean_n.T
 
     def predict(self, Xq: torch.Tensor, return_var: bool = True):
         """Posterior mean and variance at Xq (P, d) -> ((P, m), (P, m)).
@@ -426,58 +401,39 @@ class FittedGP:
         ``return_var=False`` (the per-generation surrogate-evaluate path)
         the quadratic term is skipped and (mean, None) returned.
         """
-        if not return_var and self.compute != "bf16":
-            from dmosopt_amd import ops
-
+        bf16 = self.compute == "bf16"
+        if not return_var and not bf16:
             fused = ops.gp_predict_mean_fused(
                 Xq, self.X, self.theta, self.alpha, self.y_mean, self.y_std,
                 self.nu, self.anisotropic,
             )
             if fused is not None:
                 return fused, None
-        if return_var and self._fused_var_ok(Xq):
-            from dmosopt_amd import ops
-
-            mv = ops.gp_predict_mean_var_fused(
-                Xq, self.X, self.theta, self.alpha, self.Linv, self.y_mean,
-                self.y_std, self.nu, self.anisotropic,
-            )
-            # The variance comes from the fused block. The mean keeps the
-            # bmm chain this method always had: evaluate() of a mean-only
-            # model comes through here too (the inner loop's initial
-            # population), and the gemv sums in another order — last-bit
-            # differences there change every later generation.
-            Ks = build_kernel(Xq, self.X, self.theta, nu=self.nu,
-                              anisotropic=self.anisotropic)
+        # deterministic CPU math (thread-team-independent): the replicated-
+        # rank scheme compares these values across processes
+        with _single_threaded_cpu_math(not Xq.is_cuda):
+            if bf16:
+                Ks = ops.matern_cross_bf16_kernel(
+                    Xq.float(), self.X, self.theta, self.nu, self.anisotropic
+                )
+            else:
+                Ks = build_kernel(Xq, self.X, self.theta, nu=self.nu,
+                                  anisotropic=self.anisotropic)
+            # The mean stays on this bmm chain with return_var=True as well:
+            # evaluate() of a mean-only model comes through here (the inner
+            # loop's initial population), and the fused gemv sums in another
+            # order — last-bit differences there change every later
+            # generation.
             mean_n = torch.bmm(Ks, self.alpha)[:, :, 0]  # (m, P)
-            mean = self.y_mean[None, :] + self.y_std[None, :] * mean_n.T
-            return mean, mv[:, self.theta.shape[0]:]
-        if self.compute == "bf16":
-            from dmosopt_amd import ops
-
-            Ks = ops.matern_cross_bf16_kernel(
-                Xq.float(), self.X, self.theta, self.nu, self.anisotropic
-            )
-        elif not Xq.is_cuda:
-            # deterministic CPU math (thread-team-independent): the
-            # replicated-rank scheme compares these values across processes
-            with _single_threaded_cpu_math(True):
-                return self._predict_torch(Xq, return_var)
-        else:
-            Ks = build_kernel(Xq, self.X, self.theta, nu=self.nu, anisotropic=self.anisotropic)
-        # (m, P, N)
-        mean_n = torch.bmm(Ks, self.alpha)[:, :, 0]  # (m, P)
-        if not return_var:
-            return self.y_mean[None, :] + self.y_std[None, :] * mean_n.T, None
-        return self._finish_var(Xq, Ks, mean_n)
-
-    def _predict_torch(self, Xq, return_var):
-        Ks = build_kernel(Xq, self.X, self.theta, nu=self.nu,
-                          anisotropic=self.anisotropic)
-        mean_n = torch.bmm(Ks, self.alpha)[:, :, 0]  # (m, P)
-        if not return_var:
-            return self.y_mean[None, :] + self.y_std[None, :] * mean_n.T, None
-        return self._finish_var(Xq, Ks, mean_n)
+            if not return_var:
+                return self._destandardize(mean_n), None
+            if self.compute == "fp32" and ops.native_fp32(Xq, self.X):
+                mv = ops.gp_predict_mean_var_fused(
+                    Xq, self.X, self.theta, self.alpha, self.Linv, self.y_mean,
+                    self.y_std, self.nu, self.anisotropic,
+                )
+                return self._destandardize(mean_n), mv[:, self.theta.shape[0]:]
+            return self._finish_var(Xq, Ks, mean_n)
 
     def _finish_var(self, Xq, Ks, mean_n):
         sf2 = torch.exp(self.theta[:, 0])
@@ -490,6 +446,5 @@ class FittedGP:
             v = torch.linalg.solve_triangular(self.L, Ks.transpose(-1, -2), upper=False)
             quad = (v * v).sum(dim=1)
         var_n = (kss - quad).clamp_min(0.0)  # (m, P)
-        mean = self.y_mean[None, :] + self.y_std[None, :] * mean_n.T
         var = (self.y_std[None, :] ** 2) * var_n.T
-        return mean, var
+        return self._destandardize(mean_n), var

@@ -116,7 +116,6 @@ def sceua_batched(
             lds = (npg * 2 + npg * nopt) * 4
             use_native_stage = lds <= 60 * 1024
     if use_native_stage:
-        from dmosopt_amd import _hipops as _hip
         bl_f = bl_t.to(torch.float32).contiguous()
         bu_f = bu_t.to(torch.float32).contiguous()
 
@@ -158,11 +157,11 @@ def sceua_batched(
             icall_i32 = torch.zeros(S, dtype=torch.int32, device=device)
             for _step in range(nspl):
                 lcs = lcs_all[_step].contiguous()
-                cand = _hip.sceua_propose(
+                cand = _ops.sceua_propose(
                     cx, lcs, bl_f, bu_f, nps, int(rng.integers(0, 2**62))
                 )
                 fall = func(cand.reshape(3 * S * G, nopt), sid3)
-                ok = _hip.sceua_accept(
+                ok = _ops.sceua_accept(
                     cx, cf, cand, fall.to(torch.float32).contiguous(), lcs,
                     act_i32, icall_i32, nps,
                 )

@@ -68,6 +68,20 @@ def _use_native(*tensors: torch.Tensor) -> bool:
     return True
 
 
+def native_fp32(*tensors: torch.Tensor) -> bool:
+    """The gate of the float32 native paths: every tensor is a float32 GPU
+    tensor, the torch path is not forced and the native extension is loaded
+    (a GPU tensor without the extension is an error, as in every op here)."""
+    return all(
+        t.is_cuda and t.dtype == torch.float32 for t in tensors
+    ) and _use_native(*tensors)
+
+
+def _nu_arg(nu) -> float:
+    """Matern nu as the native bindings take it: 0.0 stands for RBF."""
+    return 0.0 if (nu is None or nu == float("inf")) else float(nu)
+
+
 # ------------------------------------------------------------------ ranking
 def pareto_rank(Y: torch.Tensor) -> torch.Tensor:
     if _use_native(Y):
@@ -79,37 +93,6 @@ def pareto_rank(Y: torch.Tensor) -> torch.Tensor:
         # (round-2 lesson, NOTES.md).
         return _native.pareto_rank(Y.contiguous().float())
     return torch_ref.pareto_rank(Y)
-
-
-def _pareto_rank_gpu(Y: torch.Tensor) -> torch.Tensor:
-    """GPU ranking: native fused dominance-degree matrix, then a
-    dominator-count peel driven by one float matvec per front (O(N^2) GEMV
-    work per front is microseconds on-device; the former per-front full
-    column-max scan was O(N^2) int traffic x #fronts — 208 ms at N=8192 on
-    many-front problems). Syncs amortized over 16-front chases."""
-    n, m = Y.shape
-    if n == 0:
-        return torch.zeros(0, dtype=torch.long, device=Y.device)
-    D = _native.dominance_degree_matrix(Y.contiguous().float())
-    # identical rows already zeroed by the native kernel (incl. diagonal)
-    Dom_f = (D == m).to(torch.float32)  # Dom[i][j]: i dominates j
-    n_dom = Dom_f.sum(dim=0)  # float counts (exact for n < 2^24)
-    rank = torch.zeros(n, dtype=torch.long, device=Y.device)
-    alive = torch.ones(n, dtype=torch.bool, device=Y.device)
-    k = 0
-    remaining = n
-    CHASE = 16
-    while remaining > 0 and k < n + CHASE:
-        for c in range(CHASE):
-            front = alive & (n_dom == 0)
-            rank = torch.where(front, torch.full_like(rank, k + c), rank)
-            alive &= ~front
-            # subtract peeled dominators' contributions with one matvec
-            n_dom = n_dom - front.to(torch.float32) @ Dom_f
-            n_dom = torch.where(alive, n_dom, torch.ones_like(n_dom))
-        k += CHASE
-        remaining = int(alive.sum().item())
-    return rank
 
 
 def dominance_degree_matrix(Y: torch.Tensor) -> torch.Tensor:
@@ -219,7 +202,7 @@ def remove_duplicates(x: torch.Tensor, y: torch.Tensor, eps: float = 1e-16):
 # ------------------------------------------------------------- variation ops
 def sbx_from_pool(pool, i1, i2, di, lo, hi, seed: int, generator=None):
     """SBX on pool rows (i1, i2) -> (child1, child2), fused RNG on GPU."""
-    if _use_native(pool) and pool.dtype == torch.float32:
+    if native_fp32(pool):
         return _native.sbx_batch(
             pool.contiguous(),
             i1.to(torch.int32).contiguous(),
@@ -234,7 +217,7 @@ def sbx_from_pool(pool, i1, i2, di, lo, hi, seed: int, generator=None):
 
 def mutation_from_pool(pool, idx, di, lo, hi, mutation_rate: float, seed: int, generator=None):
     """Polynomial mutation on pool rows idx, fused RNG on GPU."""
-    if _use_native(pool) and pool.dtype == torch.float32:
+    if native_fp32(pool):
         return _native.mutation_batch(
             pool.contiguous(),
             idx.to(torch.int32).contiguous(),
@@ -250,14 +233,37 @@ def mutation_from_pool(pool, idx, di, lo, hi, mutation_rate: float, seed: int, g
 
 
 # -------------------------------------------------------------------- GP ops
+def gp_pred_args(X, theta, alpha, y_mean, y_std, nu, anisotropic):
+    """Per-fit arguments of the native predict calls, converted once."""
+    return (
+        X.contiguous(), theta.contiguous().float(), alpha.contiguous().float(),
+        y_mean.float().contiguous(), y_std.float().contiguous(), _nu_arg(nu),
+        bool(anisotropic),
+    )
+
+
+# Native predict calls on arguments the caller holds converted already
+# (models/gp.py caches gp_pred_args per fit: the generation loop is host-
+# dispatch-bound) and after the caller has passed native_fp32 itself.
+def gp_predict_mean_cached(Xq, pred_args, q_lb, q_invrg):
+    """Posterior mean (P, B) of float32 queries (raw with q_lb / q_invrg)."""
+    return _native.gp_predict_mean(Xq, *pred_args, q_lb, q_invrg)
+
+
+def gp_predict_mean_var_cached(Xq, pred_args, Linv, q_lb, q_invrg, var_decimals):
+    """(P, 2B) block [mean | var], var = y_std^2 * max(sf2 + noise -
+    |Linv k*|^2, 0); ``var_decimals >= 0`` rounds the variance columns."""
+    return _native.gp_predict_mean_var(
+        Xq, *pred_args[:3], Linv, *pred_args[3:], q_lb, q_invrg, var_decimals
+    )
+
+
 def gp_predict_mean_fused(Xq, X, theta, alpha, y_mean, y_std, nu, anisotropic):
     """Fused normalized-query posterior mean; None when native doesn't apply."""
-    if _use_native(Xq) and X.dtype == torch.float32:
-        nu_arg = 0.0 if (nu is None or nu == float("inf")) else float(nu)
-        return _native.gp_predict_mean(
-            Xq.to(torch.float32).contiguous(), X.contiguous(), theta.contiguous().float(),
-            alpha.contiguous().float(), y_mean.float(), y_std.float(),
-            nu_arg, bool(anisotropic),
+    if Xq.is_cuda and native_fp32(X):
+        return gp_predict_mean_cached(
+            Xq.float().contiguous(),
+            gp_pred_args(X, theta, alpha, y_mean, y_std, nu, anisotropic), None, None,
         )
     return None
 
@@ -266,28 +272,32 @@ def gp_predict_mean_var_fused(
     Xq, X, theta, alpha, Linv, y_mean, y_std, nu, anisotropic,
     q_lb=None, q_invrg=None, var_decimals=-1,
 ):
-    """Fused posterior mean and variance, (P, 2B) laid out [mean | var] with
-    var = y_std^2 * max(sf2 + noise - |Linv k*|^2, 0); None when native
-    doesn't apply. ``var_decimals >= 0`` rounds the variance columns."""
-    if _use_native(Xq) and X.dtype == torch.float32:
-        nu_arg = 0.0 if (nu is None or nu == float("inf")) else float(nu)
-        return _native.gp_predict_mean_var(
-            Xq.to(torch.float32).contiguous(), X.contiguous(), theta.contiguous().float(),
-            alpha.contiguous().float(), Linv.contiguous().float(),
-            y_mean.float().contiguous(), y_std.float().contiguous(),
-            nu_arg, bool(anisotropic), q_lb, q_invrg, int(var_decimals),
+    """gp_predict_mean_var_cached on unconverted arguments; None when native
+    doesn't apply."""
+    if Xq.is_cuda and native_fp32(X):
+        return gp_predict_mean_var_cached(
+            Xq.float().contiguous(),
+            gp_pred_args(X, theta, alpha, y_mean, y_std, nu, anisotropic),
+            Linv.contiguous().float(), q_lb, q_invrg, int(var_decimals),
         )
     return None
+
+
+def sceua_propose(cx, lcs, bl, bu, nps, seed):
+    return _native.sceua_propose(cx, lcs, bl, bu, nps, seed)
+
+
+def sceua_accept(cx, cf, cand, fall, lcs, act, icall, nps):
+    return _native.sceua_accept(cx, cf, cand, fall, lcs, act, icall, nps)
 
 
 def gp_nmll_fused(X, theta, y, nu, anisotropic, jitter):
     """Fused batched GP NMLL (assemble + Cholesky + solve + reduce) in one
     extension call; None if the native path does not apply."""
-    if _use_native(X) and X.dtype == torch.float32:
-        nu_arg = 0.0 if (nu is None or nu == float("inf")) else float(nu)
+    if native_fp32(X):
         return _native.gp_nmll(
             X.contiguous(), theta.contiguous().float(), y.contiguous().float(),
-            nu_arg, bool(anisotropic), float(jitter),
+            _nu_arg(nu), bool(anisotropic), float(jitter),
         )
     return None
 
@@ -297,11 +307,10 @@ def gp_nmll_grad(X, theta, y, nu, anisotropic, jitter):
     Float32 GPU tensors run the fused native pipeline (value pipeline of
     gp_nmll, then alpha, K^-1 and the gp_nmll_grad.hip tile kernels in the
     same extension call); everything else the closed form in plain torch."""
-    if _use_native(X) and X.dtype == torch.float32:
-        nu_arg = 0.0 if (nu is None or nu == float("inf")) else float(nu)
+    if native_fp32(X):
         nmll, grad = _native.gp_nmll_grad(
             X.contiguous(), theta.contiguous().float(), y.contiguous().float(),
-            nu_arg, bool(anisotropic), float(jitter),
+            _nu_arg(nu), bool(anisotropic), float(jitter),
         )
         return nmll, grad
     return torch_ref.gp_nmll_grad_ref(X, theta, y, nu, anisotropic, jitter)
@@ -309,10 +318,9 @@ def gp_nmll_grad(X, theta, y, nu, anisotropic, jitter):
 
 def matern_train_kernel(X, theta, nu, anisotropic, jitter):
     """Batched symmetric kernel matrices K (B,N,N) with noise+jitter diag."""
-    if _use_native(X) and X.dtype == torch.float32:
-        nu_arg = 0.0 if (nu is None or nu == float("inf")) else float(nu)
+    if native_fp32(X):
         return _native.matern_train(
-            X.contiguous(), theta.contiguous().float(), nu_arg, bool(anisotropic), float(jitter)
+            X.contiguous(), theta.contiguous().float(), _nu_arg(nu), bool(anisotropic), float(jitter)
         )
     from dmosopt_amd.models import gp_core
 
@@ -321,10 +329,9 @@ def matern_train_kernel(X, theta, nu, anisotropic, jitter):
 
 def matern_cross_kernel(Xq, X, theta, nu, anisotropic):
     """Batched cross kernel K* (B,P,N), no diagonal noise."""
-    if _use_native(X) and X.dtype == torch.float32:
-        nu_arg = 0.0 if (nu is None or nu == float("inf")) else float(nu)
+    if native_fp32(X):
         return _native.matern_cross(
-            Xq.contiguous(), X.contiguous(), theta.contiguous().float(), nu_arg, bool(anisotropic)
+            Xq.contiguous(), X.contiguous(), theta.contiguous().float(), _nu_arg(nu), bool(anisotropic)
         )
     from dmosopt_amd.models import gp_core
 
@@ -337,14 +344,13 @@ def matern_cross_bf16_kernel(Xq, X, theta, nu, anisotropic, q_lb=None, q_invrg=N
     Matern transform and output in fp32. GPU-only — no host fallback (the
     bf16 route is explicitly requested, silence would hide a missing
     extension)."""
-    if not (_use_native(X) and X.dtype == torch.float32):
+    if not native_fp32(X):
         raise RuntimeError(
             "matern_cross_bf16 requires the gfx950 native extension and "
             "float32 CUDA tensors"
         )
-    nu_arg = 0.0 if (nu is None or nu == float("inf")) else float(nu)
     return _native.matern_cross_bf16(
-        Xq.contiguous(), X.contiguous(), theta.contiguous().float(), nu_arg,
+        Xq.contiguous(), X.contiguous(), theta.contiguous().float(), _nu_arg(nu),
         bool(anisotropic), q_lb, q_invrg,
     )
 
@@ -353,7 +359,7 @@ def chol_factor_batched_bf16(K):
     """Batched Cholesky with the trailing SYRK updates on the bf16 matrix
     units (panels stay exact fp32). Falls back to the fp32 factorization
     when the native path is unavailable (CPU tests)."""
-    if _use_native(K) and K.dtype == torch.float32 and K.shape[1] > 32:
+    if native_fp32(K) and K.shape[1] > 32:
         logdet, info = _native.cholesky_batched_bf16_(K)
         return K, logdet, info
     return chol_factor_batched(K)
@@ -369,7 +375,7 @@ def chol_factor_batched(K):
     cholesky raises launch failures. Single large factorizations
     (N >= 1200, where rocSOLVER's multi-CU decomposition wins ~10x and
     was verified working) dispatch to torch/rocSOLVER."""
-    if _use_native(K) and K.dtype == torch.float32:
+    if native_fp32(K):
         # crossover re-measured round 2 (profiles/README.md large-N table):
         # native wins to N=2048, parity at 4096
         if K.shape[1] < 2048:
@@ -392,7 +398,7 @@ def chol_factor_multik(K, rhs=None, schedule="classic"):
     rhs); the inputs are left untouched. DMOSOPT_CHOL_LOOKAHEAD is latched
     once per process, so this is how the two schedules are compared inside
     one process. Native only: a missing extension is an error."""
-    if not (_use_native(K) and K.dtype == torch.float32):
+    if not native_fp32(K):
         raise RuntimeError("chol_factor_multik needs the native extension "
                            "and a float32 GPU tensor")
     L = K.contiguous().clone()
@@ -404,7 +410,7 @@ def chol_factor_multik(K, rhs=None, schedule="classic"):
 
 def chol_solve_batched(L, Y):
     """Solve K X = Y given the factor L (B,N,N); Y (B,N,R) -> X (B,N,R)."""
-    if _use_native(L) and L.dtype == torch.float32:
+    if native_fp32(L):
         Z = Y.contiguous().clone()
         _native.forward_solve_(L.contiguous(), Z)
         _native.backward_solve_(L.contiguous(), Z)
@@ -414,7 +420,7 @@ def chol_solve_batched(L, Y):
 
 def tri_solve_forward(L, Y):
     """Solve L Z = Y (B,N,R)."""
-    if _use_native(L) and L.dtype == torch.float32:
+    if native_fp32(L):
         Z = Y.contiguous().clone()
         _native.forward_solve_(L.contiguous(), Z)
         return Z

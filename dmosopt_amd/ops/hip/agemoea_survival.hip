@@ -21,6 +21,7 @@
 // (np.argmax parity).
 
 #include "common.h"
+#include "launchers.h"
 #include <math.h>
 
 #define AGES_TPB 256

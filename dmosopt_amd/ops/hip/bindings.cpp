@@ -6,100 +6,11 @@
 
 #include <vector>
 
+#include "launchers.h"
+
 #define CHECK_GPU(x) \
   TORCH_CHECK(x.is_cuda(), #x " must be a GPU tensor"); \
   TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
-
-extern "C" {
-void launch_matern_assemble_affine(const float*, const float*, const float*, float*, int, int, int, int, int, float, int, int, int, const float*, const float*, hipStream_t);
-void launch_gp_mean_gemv(const float*, const float*, const float*, const float*, float*, int, int, int, int, hipStream_t);
-int launch_gp_fill_identity(float*, int, int, hipStream_t);
-int gp_nmll_grad_tiles(int);
-int launch_gp_nmll_grad(const float*, const float*, const float*, const float*,
-                        const float*, const int*, float*, float*, int, int,
-                        int, int, int, int, hipStream_t);
-int launch_gp_variance(const float*, const float*, const float*, const float*,
-                       float*, float*, int, int, int, int, float, hipStream_t);
-void launch_matern_assemble(const float*, const float*, const float*, float*,
-                            int, int, int, int, int, float, int, int, int,
-                            hipStream_t);
-void launch_cholesky_batched(float*, float*, int*, int, int, hipStream_t);
-void launch_cholesky_multik_sched(float*, float*, int*, float*, int, int, int,
-                                  hipStream_t);
-int launch_cholesky_fused_solve(float*, float*, int*, float*, int, int,
-                                hipStream_t);
-void launch_forward_solve_batched(const float*, float*, int, int, int,
-                                  hipStream_t);
-void launch_backward_solve_batched(const float*, float*, int, int, int,
-                                   hipStream_t);
-void launch_dominance_matrix(const float*, int*, int, int, hipStream_t);
-void launch_peel_front(const int*, const unsigned char*, unsigned char*, int*,
-                       int, int, hipStream_t);
-void launch_commit_front(const unsigned char*, unsigned char*, int*, int, int,
-                         hipStream_t);
-void launch_crowding(const float*, float*, int, int, hipStream_t);
-void launch_sbx_batch(const float*, const int*, const int*, const float*,
-                      const float*, const float*, float*, int, int,
-                      unsigned long long, hipStream_t);
-void launch_mutation_batch(const float*, const int*, const float*,
-                           const float*, const float*, float*, int, int, float,
-                           unsigned long long, hipStream_t);
-void launch_hv_mc_uniform(const float*, const float*, const float*,
-                          unsigned long long*, long long, int, int,
-                          unsigned long long, hipStream_t);
-void launch_hv_fpras(const float*, const float*, const float*,
-                     unsigned long long*, long long, int, int,
-                     unsigned long long, hipStream_t);
-void launch_cmaes_update(float*, float*, float*, const float*, const float*,
-                         int, int, float, float, float, hipStream_t);
-int launch_peel_from_y(const float*, int*, int, int, hipStream_t);
-void launch_nmll_reduce(const float*, const float*, const int*, float*, int, int, float, hipStream_t);
-void launch_sceua_propose(const float*, const int*, const float*, const float*, float*, int, int, int, int, int, unsigned long long, hipStream_t);
-int launch_sceua_accept(float*, float*, const float*, const float*, const int*, const int*, int*, int, int, int, int, int, hipStream_t);
-int launch_tournament(const float*, const long long*, float*, long long*, int, int, int, float, unsigned long long, hipStream_t);
-void launch_tournament_keys(float*, int, float, unsigned long long, hipStream_t);
-int launch_survivor_count(const long long*, const long long*, int, int, int, long long*, long long*, hipStream_t);
-void launch_pack_rank_crowd(const long long*, const float*, long long*, int, hipStream_t);
-int launch_rank_crowd_sort(const long long*, const float*, long long*, int,
-                           int, hipStream_t);
-void launch_variation_slots(const float*, const long long*, const long long*, const long long*, const long long*, const float*, const float*, const float*, const float*, float*, int, int, int, float, unsigned long long, unsigned long long, hipStream_t);
-void launch_variation_events(const float*, const long long*, const long long*, const long long*, const long long*, const long long*, const float*, const float*, const float*, const float*, float*, int, int, int, float, unsigned long long, unsigned long long, hipStream_t);
-void launch_gather3(const float*, const float*, const long long*, const long long*, float*, float*, long long*, int, int, int, hipStream_t);
-int launch_peel_bits(const float*, unsigned int*, int*, int, int, hipStream_t);
-int launch_coop_peel(const float*, unsigned int*, unsigned int*, int*, int*,
-                     int*, int, int, int, hipStream_t);
-void launch_peel_single_block(const int*, int*, int, int, hipStream_t);
-void launch_hv2d(const double*, const double*, double*, int, hipStream_t);
-void launch_hv3d_slices(const double*, const double*, const double*,
-                        const double*, double*, int, hipStream_t);
-void launch_ehvi(const double*, const double*, const double*, const double*,
-                 double*, int, int, int, hipStream_t);
-void launch_lacour_flags(const double*, const long long*, const double*,
-                         const double*, unsigned char*, unsigned char*, int,
-                         int, hipStream_t);
-void launch_lacour_scatter(const double*, const long long*, const double*,
-                           const unsigned char*, const unsigned char*,
-                           const long long*, const long long*,
-                           const long long*, long long, long long, double*,
-                           long long*, int, int, hipStream_t);
-void launch_lacour_volumes(const double*, const long long*, const double*,
-                           const double*, double*, int, int, hipStream_t);
-void launch_mfma_bf16_probe(const float*, const float*, float*, hipStream_t);
-void launch_matern_cross_bf16(const float*, const float*, const float*,
-                              float*, int, int, int, int, int, int, int,
-                              const float*, const float*, hipStream_t);
-void launch_cholesky_multik_bf16(float*, float*, int*, int, int, hipStream_t);
-void launch_agemoea_survival(const float*, const unsigned char*, float*, int,
-                             hipStream_t);
-void launch_minkowski_norm_matrix(const float*, float*, int, int, float,
-                                  hipStream_t);
-void launch_cat_rows(const float*, const float*, float*, long long,
-                     long long, hipStream_t);
-void launch_colsum(const float*, float*, int, int, hipStream_t);
-void launch_smpso_velocity(const float*, const float*, const float*,
-                           const float*, const float*, const float*, float*,
-                           int, int, float, float, float, float, hipStream_t);
-}
 
 static hipStream_t cur_stream() {
   return (hipStream_t)c10::hip::getCurrentHIPStream().stream();
@@ -112,121 +23,145 @@ static int nu_code(double nu) {
   return 0;  // RBF / inf
 }
 
+// ------------------------------------------------------------------ GP ops
+// The GP entry points share one argument check and one function per pipeline
+// stage, so those that promise the same bits queue the same launches by
+// construction. `fn` is the Python-visible name in the error messages. The
+// checks are flag reads: gp_predict_mean runs once per generation.
+struct GpArgs {
+  const char* fn;
+  const torch::Tensor &X, &theta;  // (N,D), (B,p)
+  int nu;
+  bool aniso;
+  int64_t N, D, B, p;
+  const float *q_lb, *q_invrg;  // per-dim affine of raw queries, or null
+};
+
+static void gp_check_f32(const char* fn, const char* name,
+                         const torch::Tensor& t) {
+  TORCH_CHECK(t.is_cuda(), fn, ": ", name, " must be a GPU tensor");
+  TORCH_CHECK(t.is_contiguous(), fn, ": ", name, " must be contiguous");
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32, fn, ": ", name,
+              " must be float32");
+}
+
+static void gp_check_launch(const char* fn, const char* stage) {
+  const hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, fn, ": ", stage, " launch failed: ",
+              hipGetErrorString(err));
+}
+
+static GpArgs gp_check_args(
+    const char* fn, const torch::Tensor& X, const torch::Tensor& theta,
+    double nu, bool aniso,
+    const c10::optional<torch::Tensor>& q_lb = c10::nullopt,
+    const c10::optional<torch::Tensor>& q_invrg = c10::nullopt) {
+  gp_check_f32(fn, "X", X);
+  gp_check_f32(fn, "theta", theta);
+  TORCH_CHECK(X.dim() == 2 && theta.dim() == 2, fn,
+              ": X (N,D) and theta (B,p) required");
+  const int64_t N = X.size(0), D = X.size(1), B = theta.size(0),
+                p = theta.size(1);
+  TORCH_CHECK(N >= 1 && B >= 1 && D >= 1, fn, ": empty input");
+  TORCH_CHECK(p == (aniso ? D + 2 : 3), fn,
+              ": theta width does not match the kernel");
+  TORCH_CHECK(q_lb.has_value() == q_invrg.has_value(), fn,
+              ": q_lb and q_invrg come together");
+  if (q_lb) {
+    gp_check_f32(fn, "q_lb", *q_lb);
+    gp_check_f32(fn, "q_invrg", *q_invrg);
+    TORCH_CHECK(q_lb->numel() == D && q_invrg->numel() == D, fn,
+                ": q_lb/q_invrg must be float32 (D,)");
+  }
+  return {fn, X, theta, nu_code(nu), aniso, N, D, B, p,
+          q_lb ? q_lb->data_ptr<float>() : nullptr,
+          q_lb ? q_invrg->data_ptr<float>() : nullptr};
+}
+
+// Targets of the NMLL calls: (N,) shared by all candidates or (B,N) rows.
+static void gp_check_targets(const GpArgs& g, const torch::Tensor& y) {
+  gp_check_f32(g.fn, "y", y);
+  TORCH_CHECK((y.dim() == 1 && y.size(0) == g.N) ||
+                  (y.dim() == 2 && y.size(0) == g.B && y.size(1) == g.N),
+              g.fn, ": y must be (N,) or (B,N)");
+}
+
+// Query-side arguments of the predict calls.
+static void gp_check_query(const GpArgs& g, const torch::Tensor& Xq,
+                           const torch::Tensor& alpha,
+                           const torch::Tensor& y_mean,
+                           const torch::Tensor& y_std) {
+  gp_check_f32(g.fn, "Xq", Xq);
+  gp_check_f32(g.fn, "alpha", alpha);
+  gp_check_f32(g.fn, "y_mean", y_mean);
+  gp_check_f32(g.fn, "y_std", y_std);
+  TORCH_CHECK(Xq.dim() == 2 && Xq.size(0) >= 1, g.fn,
+              ": Xq (P,D) with P >= 1 required");
+  TORCH_CHECK(Xq.size(1) == g.D, g.fn, ": Xq/X width mismatch");
+  TORCH_CHECK(alpha.numel() == g.B * g.N && y_mean.numel() == g.B &&
+                  y_std.numel() == g.B,
+              g.fn, ": alpha/y_mean/y_std shape mismatch");
+}
+
+// Kernel matrix (B,P,N) of Xq (P,D) against X; `form` is the launcher's
+// `symmetric` (0 cross, 1 train, 2 direct-difference cross). grid.z carries B
+// and grid.y / grid.x the 32-wide tiles; the kernel indexes its inputs with
+// ints and stages two 32 x (D|1) slabs in the default 64 KiB of LDS.
+static torch::Tensor gp_assemble(const GpArgs& g, const torch::Tensor& Xq,
+                                 int nu, int form, float jitter) {
+  const int64_t P = Xq.size(0);
+  TORCH_CHECK(g.B <= 65535 && (g.N + 31) / 32 <= 65535 &&
+                  (P + 31) / 32 <= 65535 && P * g.D < (1LL << 31) &&
+                  g.N * g.D < (1LL << 31) && g.D <= 254,
+              g.fn, ": shape exceeds the launch bounds (B <= 65535, N and P "
+              "<= 2097120, D <= 254)");
+  auto K = torch::empty({g.B, P, g.N}, g.X.options());
+  launch_matern_assemble_affine(
+      Xq.data_ptr<float>(), g.X.data_ptr<float>(), g.theta.data_ptr<float>(),
+      K.data_ptr<float>(), g.B, P, g.N, g.D, g.p, jitter, nu, g.aniso ? 1 : 0,
+      form, form == 1 ? nullptr : g.q_lb, form == 1 ? nullptr : g.q_invrg,
+      cur_stream());
+  gp_check_launch(g.fn, "kernel assembly");
+  return K;
+}
+
 torch::Tensor matern_train(torch::Tensor X, torch::Tensor theta, double nu,
                            bool aniso, double jitter) {
-  CHECK_GPU(X);
-  CHECK_GPU(theta);
-  const int N = X.size(0), D = X.size(1), B = theta.size(0);
-  auto K = torch::empty({B, N, N}, X.options());
-  launch_matern_assemble(X.data_ptr<float>(), X.data_ptr<float>(),
-                         theta.data_ptr<float>(), K.data_ptr<float>(), B, N, N,
-                         D, theta.size(1), (float)jitter, nu_code(nu),
-                         aniso ? 1 : 0, 1, cur_stream());
-  return K;
+  const GpArgs g = gp_check_args("matern_train", X, theta, nu, aniso);
+  return gp_assemble(g, X, g.nu, 1, (float)jitter);
 }
 
 torch::Tensor matern_cross(torch::Tensor Xq, torch::Tensor X,
                            torch::Tensor theta, double nu, bool aniso) {
-  CHECK_GPU(Xq);
-  CHECK_GPU(X);
-  CHECK_GPU(theta);
-  const int P = Xq.size(0), N = X.size(0), D = X.size(1), B = theta.size(0);
-  auto K = torch::empty({B, P, N}, X.options());
-  launch_matern_assemble(Xq.data_ptr<float>(), X.data_ptr<float>(),
-                         theta.data_ptr<float>(), K.data_ptr<float>(), B, P, N,
-                         D, theta.size(1), 0.f, nu_code(nu), aniso ? 1 : 0, 0,
-                         cur_stream());
-  return K;
+  const GpArgs g = gp_check_args("matern_cross", X, theta, nu, aniso);
+  gp_check_f32(g.fn, "Xq", Xq);
+  TORCH_CHECK(Xq.dim() == 2 && Xq.size(1) == g.D, g.fn, ": Xq/X width mismatch");
+  return gp_assemble(g, Xq, g.nu, 0, 0.f);
 }
 
-// Fused GP negative log marginal likelihood for a batch of theta: kernel
-// assembly -> batched Cholesky -> forward solve -> reduction, all queued
-// from ONE python call (the per-stage torch dispatch chain was ~40% of the
-// SCE-UA fit's host time). y: (N,) shared or (B, N) per-candidate.
-torch::Tensor gp_nmll(torch::Tensor X, torch::Tensor theta, torch::Tensor y,
-                      double nu, bool aniso, double jitter) {
-  CHECK_GPU(X);
-  CHECK_GPU(theta);
-  CHECK_GPU(y);
-  const int N = X.size(0), D = X.size(1), B = theta.size(0);
-  auto K = torch::empty({B, N, N}, X.options());
-  launch_matern_assemble(X.data_ptr<float>(), X.data_ptr<float>(),
-                         theta.data_ptr<float>(), K.data_ptr<float>(), B, N, N,
-                         D, theta.size(1), (float)jitter, nu_code(nu),
-                         aniso ? 1 : 0, 1, cur_stream());
-  auto logdet = torch::empty({B}, X.options());
-  auto info = torch::zeros({B}, X.options().dtype(torch::kInt32));
+// NMLL value pipeline: kernel assembly -> batched Cholesky with the forward
+// solve of y -> reduction, all queued from ONE python call (the per-stage
+// torch dispatch chain was ~40% of the SCE-UA fit's host time). K holds the
+// factor L, Z = L^-1 y (B,N,1), info the factorization flags, out the NMLL
+// (B,), +inf where the factorization failed.
+struct NmllPipeline {
+  torch::Tensor K, Z, info, out;
+};
+
+static NmllPipeline gp_nmll_pipeline(const GpArgs& g, const torch::Tensor& y,
+                                     double jitter) {
+  auto stream = cur_stream();
+  const int B = g.B, N = g.N;
+  auto K = gp_assemble(g, g.X, g.nu, 1, (float)jitter);
+  auto logdet = torch::empty({g.B}, g.X.options());
+  auto info = torch::zeros({g.B}, g.X.options().dtype(torch::kInt32));
   torch::Tensor Z = (y.dim() == 1)
-                        ? y.unsqueeze(0).expand({B, N}).contiguous()
+                        ? y.unsqueeze(0).expand({g.B, g.N}).contiguous()
                         : y.contiguous().clone();
-  Z = Z.view({B, N, 1});
+  Z = Z.view({g.B, g.N, 1});
   // fused factor+solve: the rhs rides the multik launch chain (panel solves
   // its 32-entry segment, the SYRK's diagonal tiles apply the trailing
   // update) — no separate ~61 us serial TRSV kernel per NMLL
-  if (launch_cholesky_fused_solve(K.data_ptr<float>(),
-                                  logdet.data_ptr<float>(),
-                                  info.data_ptr<int>(), Z.data_ptr<float>(),
-                                  B, N, cur_stream()) != 0) {
-    launch_cholesky_batched(K.data_ptr<float>(), logdet.data_ptr<float>(),
-                            info.data_ptr<int>(), B, N, cur_stream());
-    launch_forward_solve_batched(K.data_ptr<float>(), Z.data_ptr<float>(), B,
-                                 N, 1, cur_stream());
-  }
-  auto out = torch::empty({B}, X.options());
-  const float c = 0.5f * (float)N * 1.8378770664093453f;  // log(2*pi)
-  launch_nmll_reduce(Z.data_ptr<float>(), logdet.data_ptr<float>(),
-                     info.data_ptr<int>(), out.data_ptr<float>(), B, N, c,
-                     cur_stream());
-  return out;
-}
-
-// Fused NMLL value AND analytic gradient for a batch of theta. The value
-// pipeline is gp_nmll's, launch for launch (same kernels, same order, same
-// fallback branch), so nmll is bitwise what gp_nmll returns; the gradient
-// stages follow it on the same stream: backward solve for alpha, K^-1 by the
-// forward and backward solves on an identity right-hand side, then the tile
-// kernels of gp_nmll_grad.hip. Returns {nmll (B,), grad (B,p)}; a candidate
-// whose factorization failed gets +inf and a zero gradient row.
-std::vector<torch::Tensor> gp_nmll_grad(torch::Tensor X, torch::Tensor theta,
-                                        torch::Tensor y, double nu,
-                                        bool aniso, double jitter) {
-  CHECK_GPU(X);
-  CHECK_GPU(theta);
-  CHECK_GPU(y);
-  TORCH_CHECK(X.dim() == 2 && theta.dim() == 2,
-              "gp_nmll_grad: X (N,D) and theta (B,p) required");
-  for (const auto& t : {X, theta, y})
-    TORCH_CHECK(t.dtype() == torch::kFloat32,
-                "gp_nmll_grad: float32 tensors required");
-  const int64_t N = X.size(0), D = X.size(1), B = theta.size(0),
-                p = theta.size(1);
-  TORCH_CHECK(N >= 1 && B >= 1 && D >= 1, "gp_nmll_grad: empty input");
-  TORCH_CHECK(p == (aniso ? D + 2 : 3),
-              "gp_nmll_grad: theta width does not match the kernel");
-  TORCH_CHECK((y.dim() == 1 && y.size(0) == N) ||
-                  (y.dim() == 2 && y.size(0) == B && y.size(1) == N),
-              "gp_nmll_grad: y must be (N,) or (B,N)");
-  // grid.y / grid.x carry B in the gradient, assemble and solve launches and
-  // grid.y the N right-hand sides of the K^-1 solves; the slabs of a tile
-  // pair (2 x 32 x (D|1) floats) stay inside the default 64 KiB of LDS
-  TORCH_CHECK(B <= 65535 && N <= 65535 && D <= 128,
-              "gp_nmll_grad: shape exceeds the launch bounds (B, N <= 65535, "
-              "D <= 128)");
-  auto stream = cur_stream();
-  auto K = torch::empty({B, N, N}, X.options());
-  launch_matern_assemble(X.data_ptr<float>(), X.data_ptr<float>(),
-                         theta.data_ptr<float>(), K.data_ptr<float>(), B, N, N,
-                         D, p, (float)jitter, nu_code(nu), aniso ? 1 : 0, 1,
-                         stream);
-  hipError_t err = hipGetLastError();
-  TORCH_CHECK(err == hipSuccess, "gp_nmll_grad: assemble launch failed: ",
-              hipGetErrorString(err));
-  auto logdet = torch::empty({B}, X.options());
-  auto info = torch::zeros({B}, X.options().dtype(torch::kInt32));
-  torch::Tensor Z = (y.dim() == 1)
-                        ? y.unsqueeze(0).expand({B, N}).contiguous()
-                        : y.contiguous().clone();
-  Z = Z.view({B, N, 1});
   if (launch_cholesky_fused_solve(K.data_ptr<float>(),
                                   logdet.data_ptr<float>(),
                                   info.data_ptr<int>(), Z.data_ptr<float>(),
@@ -236,76 +171,115 @@ std::vector<torch::Tensor> gp_nmll_grad(torch::Tensor X, torch::Tensor theta,
     launch_forward_solve_batched(K.data_ptr<float>(), Z.data_ptr<float>(), B,
                                  N, 1, stream);
   }
-  auto out = torch::empty({B}, X.options());
+  auto out = torch::empty({g.B}, g.X.options());
   const float c = 0.5f * (float)N * 1.8378770664093453f;  // log(2*pi)
   launch_nmll_reduce(Z.data_ptr<float>(), logdet.data_ptr<float>(),
                      info.data_ptr<int>(), out.data_ptr<float>(), B, N, c,
                      stream);
-  err = hipGetLastError();
-  TORCH_CHECK(err == hipSuccess, "gp_nmll_grad: NMLL pipeline launch failed: ",
-              hipGetErrorString(err));
-  // alpha = L^-T z, in place (the reduce above has read z)
-  launch_backward_solve_batched(K.data_ptr<float>(), Z.data_ptr<float>(), B,
-                                N, 1, stream);
-  auto Kinv = torch::empty({B, N, N}, X.options());
-  int rc = launch_gp_fill_identity(Kinv.data_ptr<float>(), B, N, stream);
-  TORCH_CHECK(rc == 0, "gp_nmll_grad: identity fill launch failed: ",
-              hipGetErrorString((hipError_t)rc));
-  launch_forward_solve_batched(K.data_ptr<float>(), Kinv.data_ptr<float>(), B,
-                               N, N, stream);
-  launch_backward_solve_batched(K.data_ptr<float>(), Kinv.data_ptr<float>(),
-                                B, N, N, stream);
-  err = hipGetLastError();
-  TORCH_CHECK(err == hipSuccess, "gp_nmll_grad: solve launch failed: ",
-              hipGetErrorString(err));
-  auto part = torch::empty({B, (int64_t)gp_nmll_grad_tiles((int)N), p},
-                           X.options());
-  auto grad = torch::empty({B, p}, X.options());
-  rc = launch_gp_nmll_grad(
-      X.data_ptr<float>(), theta.data_ptr<float>(), Kinv.data_ptr<float>(),
-      Z.data_ptr<float>(), out.data_ptr<float>(), info.data_ptr<int>(),
-      part.data_ptr<float>(), grad.data_ptr<float>(), B, N, D, p, nu_code(nu),
-      aniso ? 1 : 0, stream);
-  TORCH_CHECK(rc == 0, "gp_nmll_grad: gradient kernel launch failed: ",
-              hipGetErrorString((hipError_t)rc));
-  return {out, grad};
+  gp_check_launch(g.fn, "NMLL pipeline");
+  return {K, Z, info, out};
 }
 
-// Fused posterior-mean predict for the inner-MOEA surrogate evaluate:
-// cross-kernel assembly + bmm(alpha) + de-standardization queued from one
-// python call (the torch op chain costs ~0.1 ms of dispatch per
-// generation). Xq must already be normalized to the unit box.
+// Fused GP negative log marginal likelihood for a batch of theta.
+// y: (N,) shared or (B, N) per-candidate.
+torch::Tensor gp_nmll(torch::Tensor X, torch::Tensor theta, torch::Tensor y,
+                      double nu, bool aniso, double jitter) {
+  const GpArgs g = gp_check_args("gp_nmll", X, theta, nu, aniso);
+  gp_check_targets(g, y);
+  return gp_nmll_pipeline(g, y, jitter).out;
+}
+
+// Fused NMLL value AND analytic gradient for a batch of theta. The value is
+// gp_nmll's pipeline; the gradient stages follow it on the same stream:
+// backward solve for alpha, K^-1 by the forward and backward solves on an
+// identity right-hand side, then the tile kernels of gp_nmll_grad.hip.
+// Returns {nmll (B,), grad (B,p)}; a candidate whose factorization failed
+// gets +inf and a zero gradient row.
+std::vector<torch::Tensor> gp_nmll_grad(torch::Tensor X, torch::Tensor theta,
+                                        torch::Tensor y, double nu,
+                                        bool aniso, double jitter) {
+  const GpArgs g = gp_check_args("gp_nmll_grad", X, theta, nu, aniso);
+  gp_check_targets(g, y);
+  // grid.y carries the N right-hand sides of the K^-1 solves; the gradient
+  // kernel's slabs of a tile pair (2 x 32 x (D|1) floats) stay inside the
+  // default 64 KiB of LDS
+  TORCH_CHECK(g.N <= 65535 && g.D <= 128, g.fn,
+              ": shape exceeds the launch bounds of the gradient stages "
+              "(N <= 65535, D <= 128)");
+  auto v = gp_nmll_pipeline(g, y, jitter);
+  auto stream = cur_stream();
+  const int B = g.B, N = g.N;
+  // alpha = L^-T z, in place (the reduce has read z)
+  launch_backward_solve_batched(v.K.data_ptr<float>(), v.Z.data_ptr<float>(),
+                                B, N, 1, stream);
+  auto Kinv = torch::empty({g.B, g.N, g.N}, X.options());
+  int rc = launch_gp_fill_identity(Kinv.data_ptr<float>(), B, N, stream);
+  TORCH_CHECK(rc == 0, g.fn, ": identity fill launch failed: ",
+              hipGetErrorString((hipError_t)rc));
+  launch_forward_solve_batched(v.K.data_ptr<float>(), Kinv.data_ptr<float>(),
+                               B, N, N, stream);
+  launch_backward_solve_batched(v.K.data_ptr<float>(), Kinv.data_ptr<float>(),
+                                B, N, N, stream);
+  gp_check_launch(g.fn, "solve");
+  auto part =
+      torch::empty({g.B, (int64_t)gp_nmll_grad_tiles(N), g.p}, X.options());
+  auto grad = torch::empty({g.B, g.p}, X.options());
+  rc = launch_gp_nmll_grad(
+      X.data_ptr<float>(), theta.data_ptr<float>(), Kinv.data_ptr<float>(),
+      v.Z.data_ptr<float>(), v.out.data_ptr<float>(), v.info.data_ptr<int>(),
+      part.data_ptr<float>(), grad.data_ptr<float>(), B, N, g.D, g.p, g.nu,
+      aniso ? 1 : 0, stream);
+  TORCH_CHECK(rc == 0, g.fn, ": gradient kernel launch failed: ",
+              hipGetErrorString((hipError_t)rc));
+  return {v.out, grad};
+}
+
+// Predict front end: the affine cross kernel Ks (B,P,N), then the fused
+// matvec + de-standardization into columns [0, B) of a fresh (P, cols) block,
+// cols being the output row stride: one kernel instead of bmm + addcmul +
+// transpose-contiguous. The gemv indexes its rows with ints.
+struct PredictFront {
+  torch::Tensor Ks, out;
+};
+
+static PredictFront gp_predict_front(const GpArgs& g, const torch::Tensor& Xq,
+                                     const torch::Tensor& alpha,
+                                     const torch::Tensor& y_mean,
+                                     const torch::Tensor& y_std,
+                                     int64_t cols) {
+  gp_check_query(g, Xq, alpha, y_mean, y_std);
+  const int64_t P = Xq.size(0);
+  TORCH_CHECK(g.B * P < (1LL << 31), g.fn,
+              ": shape exceeds the launch bounds (B * P < 2^31)");
+  auto Ks = gp_assemble(g, Xq, g.nu, 0, 0.0f);
+  auto out = torch::empty({P, cols}, g.X.options());
+  launch_gp_mean_gemv(Ks.data_ptr<float>(), alpha.data_ptr<float>(),
+                      y_mean.data_ptr<float>(), y_std.data_ptr<float>(),
+                      out.data_ptr<float>(), g.B, P, g.N, cols, cur_stream());
+  gp_check_launch(g.fn, "mean gemv");
+  return {Ks, out};
+}
+
+// Fused posterior-mean predict for the inner-MOEA surrogate evaluate, (P, B),
+// queued from one python call (the torch op chain costs ~0.1 ms of dispatch
+// per generation). q_lb / q_invrg normalize RAW queries inside the kernel
+// load; without them Xq must already be normalized to the unit box.
 torch::Tensor gp_predict_mean(torch::Tensor Xq, torch::Tensor X,
                               torch::Tensor theta, torch::Tensor alpha,
                               torch::Tensor y_mean, torch::Tensor y_std,
                               double nu, bool aniso,
                               c10::optional<torch::Tensor> q_lb = c10::nullopt,
                               c10::optional<torch::Tensor> q_invrg = c10::nullopt) {
-  CHECK_GPU(Xq);
-  CHECK_GPU(X);
-  const int P = Xq.size(0), N = X.size(0), D = X.size(1), B = theta.size(0);
-  auto Ks = torch::empty({B, P, N}, X.options());
-  // optional per-dim affine normalizes RAW queries inside the kernel load
-  launch_matern_assemble_affine(
-      Xq.data_ptr<float>(), X.data_ptr<float>(), theta.data_ptr<float>(),
-      Ks.data_ptr<float>(), B, P, N, D, theta.size(1), 0.0f, nu_code(nu),
-      aniso ? 1 : 0, 0, q_lb ? q_lb->data_ptr<float>() : nullptr,
-      q_invrg ? q_invrg->data_ptr<float>() : nullptr, cur_stream());
-  // fused matvec + de-standardization into the contiguous (P, B) result:
-  // one kernel instead of bmm + addcmul + transpose-contiguous
-  auto out = torch::empty({P, (long)B}, X.options());
-  launch_gp_mean_gemv(Ks.data_ptr<float>(), alpha.data_ptr<float>(),
-                      y_mean.data_ptr<float>(), y_std.data_ptr<float>(),
-                      out.data_ptr<float>(), B, P, N, B, cur_stream());
-  return out;
+  const GpArgs g =
+      gp_check_args("gp_predict_mean", X, theta, nu, aniso, q_lb, q_invrg);
+  return gp_predict_front(g, Xq, alpha, y_mean, y_std, g.B).out;
 }
 
-// Fused mean + variance predict (optimize_mean_variance mode): ONE cross-
-// kernel assembly feeds the mean gemv (the same kernel gp_predict_mean
-// launches, writing the left half of the (P, 2B) block, so the means are
-// bitwise those of gp_predict_mean) and the |Linv k*|^2 variance kernels
-// (gp_variance.hip), which write the right half. var_decimals >= 0 rounds
-// the variance columns to that many decimals in the epilogue.
+// Fused mean + variance predict (optimize_mean_variance mode): the front end
+// of gp_predict_mean writes the left half of the (P, 2B) block, and the
+// |Linv k*|^2 variance kernels (gp_variance.hip) read the same cross kernel
+// and write the right half. var_decimals >= 0 rounds the variance columns to
+// that many decimals in the epilogue.
 torch::Tensor gp_predict_mean_var(
     torch::Tensor Xq, torch::Tensor X, torch::Tensor theta,
     torch::Tensor alpha, torch::Tensor Linv, torch::Tensor y_mean,
@@ -313,87 +287,21 @@ torch::Tensor gp_predict_mean_var(
     c10::optional<torch::Tensor> q_lb = c10::nullopt,
     c10::optional<torch::Tensor> q_invrg = c10::nullopt,
     int64_t var_decimals = -1) {
-  CHECK_GPU(Xq);
-  CHECK_GPU(X);
-  CHECK_GPU(theta);
-  CHECK_GPU(alpha);
-  CHECK_GPU(Linv);
-  CHECK_GPU(y_mean);
-  CHECK_GPU(y_std);
-  TORCH_CHECK(Xq.dim() == 2 && X.dim() == 2 && theta.dim() == 2 &&
-                  Linv.dim() == 3,
-              "gp_predict_mean_var: Xq (P,D), X (N,D), theta (B,p), Linv "
-              "(B,N,N) required");
-  const int64_t P = Xq.size(0), N = X.size(0), D = X.size(1),
-                B = theta.size(0);
-  for (const auto& t : {Xq, X, theta, alpha, Linv, y_mean, y_std})
-    TORCH_CHECK(t.dtype() == torch::kFloat32,
-                "gp_predict_mean_var: float32 tensors required");
-  TORCH_CHECK(P >= 1 && N >= 1 && B >= 1 && D >= 1,
-              "gp_predict_mean_var: empty input");
-  TORCH_CHECK(Xq.size(1) == D, "gp_predict_mean_var: Xq/X width mismatch");
-  TORCH_CHECK(theta.size(1) == (aniso ? D + 2 : 3),
-              "gp_predict_mean_var: theta width does not match the kernel");
-  TORCH_CHECK(Linv.size(0) == B && Linv.size(1) == N && Linv.size(2) == N,
-              "gp_predict_mean_var: Linv must be (B,N,N)");
-  TORCH_CHECK(alpha.numel() == B * N && y_mean.numel() == B &&
-                  y_std.numel() == B,
-              "gp_predict_mean_var: alpha/y_mean/y_std shape mismatch");
-  if (q_lb || q_invrg) {
-    TORCH_CHECK(q_lb && q_invrg, "gp_predict_mean_var: q_lb and q_invrg "
-                                 "come together");
-    CHECK_GPU((*q_lb));
-    CHECK_GPU((*q_invrg));
-    TORCH_CHECK(q_lb->dtype() == torch::kFloat32 &&
-                    q_invrg->dtype() == torch::kFloat32 &&
-                    q_lb->numel() == D && q_invrg->numel() == D,
-                "gp_predict_mean_var: q_lb/q_invrg must be float32 (D,)");
-  }
-  // grid.z carries B and grid.y the tiles; the launch dims are ints
-  // grid.z carries B and grid.y the row / query tiles; the cross kernel
-  // indexes its inputs with ints and stages two 32 x (D|1) slabs in the
-  // default 64 KiB of LDS
-  TORCH_CHECK(B <= 65535 && (N + 31) / 32 <= 65535 &&
-                  (P + 31) / 32 <= 65535 && B * P < (1LL << 31) &&
-                  P * D < (1LL << 31) &&
-                  N * D < (1LL << 31) && D <= 254,
-              "gp_predict_mean_var: shape exceeds the launch bounds "
-              "(B <= 65535, N and P <= 2097120, D <= 254)");
-  TORCH_CHECK(var_decimals <= 9, "gp_predict_mean_var: var_decimals <= 9");
-  const int T = (int)((N + 31) / 32);
-  auto Ks = torch::empty({B, P, N}, X.options());
-  launch_matern_assemble_affine(
-      Xq.data_ptr<float>(), X.data_ptr<float>(), theta.data_ptr<float>(),
-      Ks.data_ptr<float>(), B, P, N, D, theta.size(1), 0.0f, nu_code(nu),
-      aniso ? 1 : 0, 0, q_lb ? q_lb->data_ptr<float>() : nullptr,
-      q_invrg ? q_invrg->data_ptr<float>() : nullptr, cur_stream());
-  hipError_t err = hipGetLastError();
-  TORCH_CHECK(err == hipSuccess, "gp_predict_mean_var: cross-kernel launch "
-                                 "failed: ", hipGetErrorString(err));
-  auto out = torch::empty({P, 2 * B}, X.options());
-  launch_gp_mean_gemv(Ks.data_ptr<float>(), alpha.data_ptr<float>(),
-                      y_mean.data_ptr<float>(), y_std.data_ptr<float>(),
-                      out.data_ptr<float>(), B, P, N, 2 * B, cur_stream());
-  err = hipGetLastError();
-  TORCH_CHECK(err == hipSuccess, "gp_predict_mean_var: mean gemv launch "
-                                 "failed: ", hipGetErrorString(err));
+  const GpArgs g =
+      gp_check_args("gp_predict_mean_var", X, theta, nu, aniso, q_lb, q_invrg);
+  gp_check_f32(g.fn, "Linv", Linv);
+  TORCH_CHECK(Linv.dim() == 3 && Linv.size(0) == g.B && Linv.size(1) == g.N &&
+                  Linv.size(2) == g.N,
+              g.fn, ": Linv must be (B,N,N)");
+  TORCH_CHECK(var_decimals <= 9, g.fn, ": var_decimals <= 9");
+  auto f = gp_predict_front(g, Xq, alpha, y_mean, y_std, 2 * g.B);
   // nu = 1/2 only: its kernel has an infinite slope in d2 at 0, so the
   // ~1e-7 cancellation of the norms-form d2 costs ~7e-4 of variance at a
   // query on a training point. The variance then reads a direct-difference
   // cross kernel; the mean keeps the norms form (gp_predict_mean's bits).
-  torch::Tensor Kv = Ks;
-  if (nu_code(nu) == 1) {
-    Kv = torch::empty({B, P, N}, X.options());
-    launch_matern_assemble_affine(
-        Xq.data_ptr<float>(), X.data_ptr<float>(), theta.data_ptr<float>(),
-        Kv.data_ptr<float>(), B, P, N, D, theta.size(1), 0.0f, 1,
-        aniso ? 1 : 0, 2, q_lb ? q_lb->data_ptr<float>() : nullptr,
-        q_invrg ? q_invrg->data_ptr<float>() : nullptr, cur_stream());
-    err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "gp_predict_mean_var: direct cross-kernel "
-                                   "launch failed: ", hipGetErrorString(err));
-  }
-  auto part = torch::empty({B, (int64_t)T, P}, X.options());
+  torch::Tensor Kv = g.nu == 1 ? gp_assemble(g, Xq, 1, 2, 0.0f) : f.Ks;
+  const int64_t P = Xq.size(0), T = (g.N + 31) / 32;  // one partial per row tile
+  auto part = torch::empty({g.B, T, P}, X.options());
   float scale = 0.f;  // 0 = no rounding
   if (var_decimals >= 0) {
     scale = 1.f;
@@ -401,11 +309,11 @@ torch::Tensor gp_predict_mean_var(
   }
   const int rc = launch_gp_variance(
       Linv.data_ptr<float>(), Kv.data_ptr<float>(), theta.data_ptr<float>(),
-      y_std.data_ptr<float>(), part.data_ptr<float>(), out.data_ptr<float>(),
-      B, P, N, theta.size(1), scale, cur_stream());
-  TORCH_CHECK(rc == 0, "gp_predict_mean_var: variance kernel launch failed: ",
+      y_std.data_ptr<float>(), part.data_ptr<float>(), f.out.data_ptr<float>(),
+      g.B, P, g.N, g.p, scale, cur_stream());
+  TORCH_CHECK(rc == 0, g.fn, ": variance kernel launch failed: ",
               hipGetErrorString((hipError_t)rc));
-  return out;
+  return f.out;
 }
 
 // Fused SCE-UA CCE stage: candidate proposal and acceptance+resort, one

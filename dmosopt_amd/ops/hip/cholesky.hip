@@ -19,6 +19,7 @@
 // chip), optionally carrying a fused forward solve.
 
 #include "common.h"
+#include "launchers.h"
 #include <math.h>
 #include <stdlib.h>
 
@@ -950,9 +951,6 @@ extern "C" void launch_cholesky_multik(float* A, float* logdet, int* info,
 // bf16-SYRK variant of the classic schedule (config-#2 precision route):
 // panels factor in exact fp32 (chol_panel_kernel), only the trailing
 // C -= P P^T runs on the bf16 matrix units (matern_bf16.hip).
-extern "C" void launch_chol_syrk_bf16(float*, int, int, int, int,
-                                      hipStream_t);
-
 extern "C" void launch_cholesky_multik_bf16(float* A, float* logdet,
                                             int* info, int B, int N,
                                             hipStream_t stream) {

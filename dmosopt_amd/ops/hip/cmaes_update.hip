@@ -12,6 +12,7 @@
 // d x d outer-product updates are grid-stride elementwise work.
 
 #include "common.h"
+#include "launchers.h"
 #include <math.h>
 
 #define CMAES_TPB 256

@@ -33,6 +33,7 @@
 // writes depends on B.
 
 #include "common.h"
+#include "launchers.h"
 #include <math.h>
 
 #define GG_TILE 32

@@ -42,6 +42,7 @@
 // (and no memset node that a captured graph could race with).
 
 #include "common.h"
+#include "launchers.h"
 #include <math.h>
 
 #define GV_TILE 32

@@ -22,6 +22,7 @@
 // decisions and the oracle tests demand <=1e-6 relative error.
 
 #include "common.h"
+#include "launchers.h"
 #include <math.h>
 
 #define HV2D_MAX_N 8192  // LDS: 8192 * 16 B = 128 KB (<160 KB per CU)

@@ -7,6 +7,7 @@
 // containment matrix is ever materialized.
 
 #include "common.h"
+#include "launchers.h"
 #include <math.h>
 
 // MCM2RV: uniform samples in [ideal, ref]; count samples dominated by any

@@ -1,0 +1,148 @@
+// The one declaration of every extern "C" launcher bindings.cpp calls, grouped by
+// the .hip file that defines it. bindings.cpp and every .hip file include it, so
+// a definition that drifts from its declaration fails to compile (C linkage has
+// no mangling: without the header the mismatch would still link).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+extern "C" {
+
+// ---------------------------------------------------------------- matern.hip
+// symmetric: 0 = cross kernel (norms form), 1 = train kernel (adds
+// noise + jitter on the diagonal), 2 = cross kernel, direct-difference form.
+// q_lb / q_invrg (both or neither): per-dim affine applied to Xq on load.
+void launch_matern_assemble_affine(const float* Xq, const float* X, const float* theta, float* K,
+    int B, int P, int N, int D, int theta_stride, float jitter, int nu_code, int aniso,
+    int symmetric, const float* q_lb, const float* q_invrg, hipStream_t stream);
+void launch_gp_mean_gemv(const float* Ks, const float* alpha, const float* y_mean,
+    const float* y_std, float* out, int B, int P, int N, int ldo, hipStream_t stream);
+
+// -------------------------------------------------------------- cholesky.hip
+void launch_nmll_reduce(const float* Z, const float* half_logdet, const int* info, float* out, int B,
+    int N, float c, hipStream_t stream);
+void launch_cholesky_multik_sched(float* A, float* logdet, int* info, float* rhs, int B, int N,
+    int sched, hipStream_t stream);
+void launch_cholesky_multik_bf16(float* A, float* logdet, int* info, int B, int N,
+    hipStream_t stream);
+// returns nonzero, launching nothing, when the fused path does not apply
+int launch_cholesky_fused_solve(float* A, float* logdet, int* info, float* rhs, int B, int N,
+    hipStream_t stream);
+void launch_cholesky_batched(float* A, float* logdet, int* info, int B, int N, hipStream_t stream);
+void launch_forward_solve_batched(const float* L, float* Y, int B, int N, int R, hipStream_t stream);
+void launch_backward_solve_batched(const float* L, float* Y, int B, int N, int R,
+    hipStream_t stream);
+
+// ----------------------------------------------------------- matern_bf16.hip
+void launch_mfma_bf16_probe(const float* A, const float* B, float* D, hipStream_t s);
+void launch_matern_cross_bf16(const float* Xq, const float* X, const float* theta, float* K, int B,
+    int P, int N, int D, int theta_stride, int nu_code, int aniso, const float* q_lb,
+    const float* q_invrg, hipStream_t stream);
+// called by cholesky.hip's bf16 schedule, not by bindings.cpp
+void launch_chol_syrk_bf16(float* A, int N, int k0, int n_pairs, int B, hipStream_t stream);
+
+// ----------------------------------------------------------- gp_variance.hip
+// launchers returning int give 0 or the hipError_t of the failed launch
+int launch_gp_variance(const float* Linv, const float* Ks, const float* theta, const float* y_std,
+    float* part, float* out, int B, int P, int N, int theta_stride, float round_scale,
+    hipStream_t stream);
+
+// ---------------------------------------------------------- gp_nmll_grad.hip
+int launch_gp_fill_identity(float* Y, int B, int N, hipStream_t stream);
+int gp_nmll_grad_tiles(int N);
+int launch_gp_nmll_grad(const float* X, const float* theta, const float* Kinv, const float* alpha,
+    const float* nmll, const int* info, float* part, float* grad, int B, int N, int D, int p,
+    int nu_code, int aniso, hipStream_t stream);
+
+// ----------------------------------------------------------- sceua_stage.hip
+void launch_sceua_propose(const float* cx, const int* lcs, const float* bl, const float* bu,
+    float* cand, int S, int G, int npg, int nopt, int nps, unsigned long long seed,
+    hipStream_t stream);
+int launch_sceua_accept(float* cx, float* cf, const float* cand, const float* fall, const int* lcs,
+    const int* act, int* icall, int S, int G, int npg, int nopt, int nps, hipStream_t stream);
+
+// ---------------------------------------------------------------- pareto.hip
+void launch_peel_single_block(const int* D, int* rank, int N, int m, hipStream_t stream);
+int launch_peel_bits(const float* Y, unsigned int* Dbits_scratch, int* rank, int N, int m,
+    hipStream_t stream);
+int launch_coop_peel(const float* Y, unsigned int* Dbits, unsigned int* fmask, int* n_dom, int* ctrl,
+    int* rank, int N, int m, int stop, hipStream_t stream);
+int launch_peel_from_y(const float* Y, int* rank, int N, int m, hipStream_t stream);
+void launch_dominance_matrix(const float* Y, int* D, int N, int m, hipStream_t stream);
+void launch_peel_front(const int* D, const unsigned char* alive, unsigned char* front, int* n_front,
+    int N, int m, hipStream_t stream);
+void launch_commit_front(const unsigned char* front, unsigned char* alive, int* rank, int k, int N,
+    hipStream_t stream);
+void launch_crowding(const float* Y, float* out, int N, int m, hipStream_t stream);
+
+// ------------------------------------------------------------- variation.hip
+void launch_sbx_batch(const float* pool, const int* p1, const int* p2, const float* di,
+    const float* lo, const float* hi, float* out, int C, int d, unsigned long long seed,
+    hipStream_t stream);
+void launch_mutation_batch(const float* pool, const int* parents, const float* di, const float* lo,
+    const float* hi, float* out, int M, int d, float mutation_rate, unsigned long long seed,
+    hipStream_t stream);
+void launch_variation_events(const float* pool, const long long* ci, const long long* mi,
+    const long long* p1, const long long* p2, const long long* im, const float* di_c,
+    const float* di_m, const float* lo, const float* hi, float* out, int C, int M, int d,
+    float mutation_rate, unsigned long long seed_sbx, unsigned long long seed_mut,
+    hipStream_t stream);
+void launch_variation_slots(const float* pool, const long long* src_rows, const long long* p1,
+    const long long* p2, const long long* im, const float* di_c, const float* di_m, const float* lo,
+    const float* hi, float* out, int total, int C, int d, float mutation_rate,
+    unsigned long long seed_sbx, unsigned long long seed_mut, hipStream_t stream);
+
+// -------------------------------------------------------------- moea_ops.hip
+void launch_tournament_keys(float* gkey, int N, float log1mp, unsigned long long seed,
+    hipStream_t stream);
+int launch_tournament(const float* population, const long long* rank, float* pool,
+    long long* pool_idx, int N, int d, int poolsize, float log1mp, unsigned long long seed,
+    hipStream_t stream);
+int launch_survivor_count(const long long* perm, const long long* c_idx, int n_perm, int n_cross,
+    int n_children, long long* succ_cross, long long* succ_mut, hipStream_t stream);
+void launch_pack_rank_crowd(const long long* rank, const float* crowd, long long* key, int N,
+    hipStream_t stream);
+void launch_gather3(const float* parm, const float* obj, const long long* rank,
+    const long long* perm, float* parm_o, float* obj_o, long long* rank_o, int pop, int d, int m,
+    hipStream_t stream);
+int launch_rank_crowd_sort(const long long* rank, const float* crowd, long long* perm, int N,
+    int pop, hipStream_t stream);
+void launch_smpso_velocity(const float* position, const float* velocity, const float* leader1,
+    const float* leader2, const float* xlb, const float* xub, float* out, int n, int d, float w,
+    float a1, float a2, float chi, hipStream_t stream);
+void launch_cat_rows(const float* a, const float* b, float* out, long long na_elems,
+    long long total_elems, hipStream_t stream);
+void launch_colsum(const float* per_dim, float* out, int m, int N, hipStream_t stream);
+
+// ------------------------------------------------------ agemoea_survival.hip
+void launch_agemoea_survival(const float* D, const unsigned char* preselected, float* crowd, int m,
+    hipStream_t s);
+void launch_minkowski_norm_matrix(const float* Y, float* D, int m, int d, float p, hipStream_t s);
+
+// ---------------------------------------------------------- cmaes_update.hip
+void launch_cmaes_update(float* A, float* Ainv, float* pc, const float* z, const float* psucc, int K,
+    int d, float cc, float ccov, float pthresh, hipStream_t stream);
+
+// ----------------------------------------------------------------- hv_mc.hip
+void launch_hv_mc_uniform(const float* P, const float* ideal, const float* ref,
+    unsigned long long* hits, long long n_samples, int N, int d, unsigned long long seed,
+    hipStream_t stream);
+void launch_hv_fpras(const float* P, const float* ref, const float* cdf, unsigned long long* hits,
+    long long n_samples, int N, int d, unsigned long long seed, hipStream_t stream);
+
+// -------------------------------------------------------------- hv_exact.hip
+void launch_hv2d(const double* P, const double* ref, double* out, int n, hipStream_t s);
+void launch_hv3d_slices(const double* Px, const double* z_thr, const double* dz, const double* ref,
+    double* out, int n, hipStream_t s);
+void launch_ehvi(const double* L, const double* U, const double* mu, const double* var, double* out,
+    int B, int nb, int d, hipStream_t s);
+void launch_lacour_flags(const double* coords, const long long* defs, const double* pts_aug,
+    const double* z, unsigned char* dominated, unsigned char* okj, int U, int d, hipStream_t s);
+void launch_lacour_scatter(const double* coords, const long long* defs, const double* z,
+    const unsigned char* dominated, const unsigned char* okj, const long long* slotA,
+    const long long* slotBj, const long long* baseBj, long long baseK, long long point_idx,
+    double* out_coords, long long* out_defs, int U, int d, hipStream_t s);
+void launch_lacour_volumes(const double* coords, const long long* defs, const double* pts_aug,
+    const double* ref, double* vol, int U, int d, hipStream_t s);
+
+}  // extern "C"

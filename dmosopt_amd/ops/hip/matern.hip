@@ -15,6 +15,7 @@
 // point; for the d <= 128 regime the kernel is bandwidth-trivial.
 
 #include "common.h"
+#include "launchers.h"
 #include <math.h>
 
 #define TILE 32
@@ -186,15 +187,6 @@ extern "C" void launch_matern_assemble_affine(
   #undef DISPATCH_AN
   #undef DISPATCH_DIRECT
   #undef DISPATCH
-}
-
-extern "C" void launch_matern_assemble(
-    const float* Xq, const float* X, const float* theta, float* K, int B,
-    int P, int N, int D, int theta_stride, float jitter, int nu_code,
-    int aniso, int symmetric, hipStream_t stream) {
-  launch_matern_assemble_affine(Xq, X, theta, K, B, P, N, D, theta_stride,
-                                jitter, nu_code, aniso, symmetric, nullptr,
-                                nullptr, stream);
 }
 
 // Fused posterior-mean GEMV + de-standardization: out[p][b] =

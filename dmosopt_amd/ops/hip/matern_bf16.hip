@@ -22,6 +22,7 @@
 // hardware against a torch matmul oracle.
 
 #include "common.h"
+#include "launchers.h"
 #include <math.h>
 
 #define TILE 32

@@ -9,6 +9,7 @@
 //                      survivor permutation                (~8 launches -> 1)
 
 #include "common.h"
+#include "launchers.h"
 #include <math.h>
 
 #define TOUR_TPB 256

@@ -17,6 +17,7 @@
 // so results are bit-identical across replicated ranks.
 
 #include "common.h"
+#include "launchers.h"
 #include <math.h>
 
 #define PTILE 32

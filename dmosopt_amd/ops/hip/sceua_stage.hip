@@ -13,6 +13,7 @@
 // ~28 fewer stream entries per stage, not their own throughput.
 
 #include "common.h"
+#include "launchers.h"
 #include <math.h>
 
 #define SCEUA_TPB 64

@@ -6,6 +6,7 @@
 // independent of launch geometry.
 
 #include "common.h"
+#include "launchers.h"
 #include <math.h>
 
 

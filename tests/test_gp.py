@@ -11,6 +11,9 @@ from dmosopt_amd.models.gp_core import batched_nmll, build_kernel, matern_from_d
 from dmosopt_amd.models.sceua import sceua_batched
 
 
+STD_ATOL = 1e-7  # posterior standard deviation against an independent oracle
+
+
 def _sklearn_gpr(X, y, theta):
     from sklearn.gaussian_process import GaussianProcessRegressor
     from sklearn.gaussian_process.kernels import ConstantKernel, Matern, WhiteKernel
@@ -60,7 +63,61 @@ def test_posterior_matches_sklearn_fixed_theta():
     )
     mean_ours, var_ours = fitted.predict(torch.as_tensor(Xq))
     assert np.allclose(mean_ours[:, 0].numpy(), mean_skl, atol=1e-8)
-    assert np.allclose(np.sqrt(var_ours[:, 0].numpy()), std_skl, atol=1e-7)
+    assert np.allclose(np.sqrt(var_ours[:, 0].numpy()), std_skl, atol=STD_ATOL)
+
+
+def _matern64(d2, nu):
+    r = torch.sqrt(d2)
+    if nu == 0.5:
+        return torch.exp(-r)
+    s = math.sqrt(5.0) * r
+    return (1.0 + s + (5.0 / 3.0) * d2) * torch.exp(-s)
+
+
+@pytest.mark.parametrize("anisotropic", [False, True])
+@pytest.mark.parametrize("nu", [0.5, 2.5])
+def test_predict_mean_same_with_and_without_variance(nu, anisotropic):
+    """predict() returns the same mean bits whether or not the variance is
+    asked for, and the variance is the closed form
+    y_std^2 * (sf2 + noise - |L^-1 k*|^2), computed here in float64 from
+    direct coordinate differences."""
+    from dmosopt_amd.models.gp_core import FittedGP
+
+    N, P, m, D, jitter = 33, 5, 2, 3, 1e-10
+    g = torch.Generator().manual_seed(33)
+    X = torch.rand(N, D, generator=g, dtype=torch.float64)
+    Xq = torch.rand(P, D, generator=g, dtype=torch.float64)
+    w = torch.rand(D, m, generator=g, dtype=torch.float64)
+    Y = 0.7 + 2.5 * torch.sin(3.0 * X @ w)
+    n_ell = D if anisotropic else 1
+    ell = 0.4 + 0.3 * torch.rand(m, n_ell, generator=g, dtype=torch.float64)
+    theta = torch.cat([
+        torch.log(torch.tensor([[1.3], [0.8]], dtype=torch.float64)),
+        torch.log(ell),
+        torch.full((m, 1), math.log(1e-3), dtype=torch.float64),
+    ], dim=1)
+    y_mean, y_std = Y.mean(dim=0), Y.std(dim=0, unbiased=False)
+    fitted = FittedGP(X, Y, theta, y_mean, y_std, nu=nu,
+                      anisotropic=anisotropic, jitter=jitter)
+
+    mean_only, none = fitted.predict(Xq, return_var=False)
+    mean, var = fitted.predict(Xq, return_var=True)
+    assert none is None
+    assert torch.equal(mean_only, mean)
+
+    want = torch.empty(P, m, dtype=torch.float64)
+    for b in range(m):
+        sf2, noise = torch.exp(theta[b, 0]), torch.exp(theta[b, -1])
+        scale = torch.exp(theta[b, 1:1 + n_ell])
+        xs, qs = X / scale, Xq / scale
+        K = sf2 * _matern64(((xs[:, None] - xs[None]) ** 2).sum(-1), nu)
+        K = K + (noise + jitter) * torch.eye(N, dtype=torch.float64)
+        Ks = sf2 * _matern64(((qs[:, None] - xs[None]) ** 2).sum(-1), nu)
+        v = torch.linalg.solve_triangular(
+            torch.linalg.cholesky(K), Ks.T, upper=False)
+        want[:, b] = y_std[b] ** 2 * (sf2 + noise - (v * v).sum(0))
+    assert (want > 0).all()
+    assert np.allclose(np.sqrt(var.numpy()), np.sqrt(want.numpy()), atol=STD_ATOL)
 
 
 def test_nmll_matches_sklearn_lml():

@@ -11,6 +11,10 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
+# fused GPU predict against the torch / host path of the same model
+PREDICT_TOL = dict(rtol=1e-3, atol=1e-3)
+
+
 @pytest.fixture(scope="module")
 def dev():
     if not torch.cuda.is_available():
@@ -472,7 +476,127 @@ def test_gp_predict_mean_fused_matches_oracle(dev):
     xq = torch.as_tensor(rng.random((33, 6)), device=dev)
     got = gp.evaluate_tensor(xq).cpu().numpy()          # fused affine path
     want, _ = gp.predict(xq.cpu().numpy())               # host oracle path
-    assert np.allclose(got, want, rtol=1e-3, atol=1e-3)
+    assert np.allclose(got, want, **PREDICT_TOL)
+
+
+# N = 33 is one element past a 32-wide tile: the smallest shape with a tile edge
+_CHECK_N, _CHECK_D, _CHECK_B, _CHECK_P = 33, 2, 2, 5
+
+
+def _gp_call_args(dev, aniso):
+    """Valid float32 GPU arguments of gp_nmll and gp_predict_mean."""
+    N, D, B, P = _CHECK_N, _CHECK_D, _CHECK_B, _CHECK_P
+    g = torch.Generator().manual_seed(33)
+    p = D + 2 if aniso else 3
+    theta = torch.cat([torch.zeros(B, 1), torch.rand(B, p - 2, generator=g) - 1.0,
+                       torch.full((B, 1), -3.0)], dim=1)
+    a = dict(
+        X=torch.rand(N, D, generator=g), Xq=torch.rand(P, D, generator=g),
+        theta=theta, y=torch.randn(N, generator=g),
+        alpha=torch.randn(B, N, 1, generator=g), y_mean=torch.randn(B, generator=g),
+        y_std=torch.rand(B, generator=g) + 0.5, q_lb=torch.zeros(D),
+        q_invrg=torch.ones(D),
+    )
+    return {k: v.float().contiguous().to(dev) for k, v in a.items()}
+
+
+def _call_nmll(a, aniso=False, **over):
+    from dmosopt_amd import _hipops
+
+    a = {**a, **over}
+    return _hipops.gp_nmll(a["X"], a["theta"], a["y"], 2.5, aniso, 1e-6)
+
+
+def _call_predict_mean(a, aniso=False, **over):
+    from dmosopt_amd import _hipops
+
+    a = {**a, **over}
+    return _hipops.gp_predict_mean(
+        a["Xq"], a["X"], a["theta"], a["alpha"], a["y_mean"], a["y_std"], 2.5,
+        aniso, a["q_lb"], a["q_invrg"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("call,name", [(_call_nmll, "gp_nmll"),
+                                       (_call_predict_mean, "gp_predict_mean")])
+def test_gp_entry_points_reject_bad_arguments(dev, call, name):
+    """gp_nmll and gp_predict_mean reject what gp_nmll_grad and
+    gp_predict_mean_var reject, and name themselves in the message."""
+    iso, ard = _gp_call_args(dev, False), _gp_call_args(dev, True)
+    for a, aniso in ((iso, False), (ard, True)):
+        out = call(a, aniso)                      # the valid call goes through
+        assert torch.isfinite(out).all()
+    with pytest.raises(RuntimeError, match=name + ": X must be a GPU tensor"):
+        call(iso, X=iso["X"].cpu())
+    with pytest.raises(RuntimeError, match=name + ": theta must be float32"):
+        call(iso, theta=iso["theta"].double())
+    with pytest.raises(RuntimeError, match=name + ": theta width"):
+        call(iso, True)                           # aniso wants D + 2 = 4 columns
+    with pytest.raises(RuntimeError, match=name + ": theta width"):
+        call(ard, False)                          # isotropic wants 3 columns
+    if call is _call_nmll:
+        with pytest.raises(RuntimeError, match="gp_nmll: y must be"):
+            call(iso, y=iso["y"][:5].contiguous())
+        with pytest.raises(RuntimeError, match="gp_nmll: y must be float32"):
+            call(iso, y=iso["y"].double())
+    else:
+        with pytest.raises(RuntimeError, match="gp_predict_mean: q_lb and q_invrg"):
+            call(iso, q_invrg=None)
+        with pytest.raises(RuntimeError, match="gp_predict_mean: alpha must be a GPU"):
+            call(iso, alpha=iso["alpha"].cpu())
+        with pytest.raises(RuntimeError, match="gp_predict_mean: y_std must be float32"):
+            call(iso, y_std=iso["y_std"].double())
+        with pytest.raises(RuntimeError, match="gp_predict_mean: q_lb/q_invrg must be"):
+            call(iso, q_lb=torch.zeros(3, device=dev), q_invrg=torch.ones(3, device=dev))
+        with pytest.raises(RuntimeError, match="gp_predict_mean: alpha/y_mean/y_std"):
+            call(iso, y_mean=iso["y_mean"][:1].contiguous())
+
+
+_FORCE_TORCH_CHILD = r"""
+import sys, numpy as np, torch
+from dmosopt_amd import ops
+from dmosopt_amd.models.gp import GPRMatern
+N, D, B, P = (int(v) for v in sys.argv[2:6])
+assert ops._FORCE_TORCH
+rng = np.random.default_rng(33)
+X = rng.random((N, D))
+Y = np.column_stack([np.sin(3.0 * X[:, 0]) + X[:, 1], X[:, 0] ** 2 - X[:, 1]])
+lb, ub = np.full(D, -0.5), np.full(D, 1.5)
+theta = np.array([[0.1, -0.7, -7.0], [-0.2, -0.4, -7.0]])
+gp = GPRMatern(X, Y, D, B, lb, ub, theta_override=theta, device="cuda")
+assert gp.dtype == torch.float32 and gp._fitted.X.is_cuda
+xq = rng.random((P, D))
+got = gp.evaluate_tensor(torch.as_tensor(xq, device="cuda"))
+assert got.is_cuda and got.dtype == torch.float32
+# forced torch: nothing on the way loaded the native extension
+assert ops._native is None, "evaluate_tensor took the native path"
+assert not gp.supports_device_mean_variance
+np.savez(sys.argv[1], got=got.cpu().numpy(), want=gp.evaluate(xq))
+"""
+
+
+@pytest.mark.gpu
+def test_force_torch_covers_evaluate_tensor(dev, tmp_path):
+    """DMOSOPT_AMD_FORCE_TORCH=1 (read at import: fresh child process) keeps
+    evaluate_tensor of a float32 GPU model on the torch path, where it agrees
+    with the model's host evaluate()."""
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    path = tmp_path / "force_torch.npz"
+    env = dict(os.environ)
+    env["DMOSOPT_AMD_FORCE_TORCH"] = "1"
+    env["PYTHONPATH"] = root + os.pathsep + env.get("PYTHONPATH", "")
+    subprocess.run(
+        [sys.executable, "-c", _FORCE_TORCH_CHILD, str(path), str(_CHECK_N),
+         str(_CHECK_D), str(_CHECK_B), str(_CHECK_P)],
+        check=True, env=env, cwd=root, timeout=120)
+    r = np.load(path)
+    assert r["got"].shape == (_CHECK_P, _CHECK_B)
+    assert np.isfinite(r["want"]).all()
+    assert np.allclose(r["got"], r["want"], **PREDICT_TOL)
 
 
 @pytest.mark.gpu

@@ -352,3 +352,11 @@ def test_ops_degenerate_shapes():
     # single objective column: total order by value
     y1 = torch.tensor([[3.0], [1.0], [2.0]])
     assert ops.pareto_rank(y1).tolist() == [2, 0, 1]
+
+
+def test_nu_arg_maps_rbf_to_zero():
+    assert ops._nu_arg(None) == 0.0
+    assert ops._nu_arg(float("inf")) == 0.0
+    for nu in (0.5, 1.5, 2.5):
+        assert ops._nu_arg(nu) == nu
+    assert isinstance(ops._nu_arg(2.5), float)
