@@ -61,6 +61,7 @@ surrogate_registry = {
 
 sensitivity_registry = {
     "dgsm": "dmosopt_amd.models.sa.SA_DGSM",
+    "dgsm_grad": "dmosopt_amd.models.sa.SA_DGSM_Grad",
     "fast": "dmosopt_amd.models.sa.SA_FAST",
 }
 

@@ -413,6 +413,32 @@ class _GPRBase:
         mean, _ = self._fitted.predict(xq, return_var=self.return_mean_variance)
         return mean
 
+    def gradient_tensor(self, x: torch.Tensor) -> torch.Tensor:
+        """Device-resident gradient of the posterior mean in the query point:
+        raw x (P, d) -> (P, m, d), [p, b, k] = d mean_b(x_p) / d x_k in raw
+        input units, no host trip. The analytic closed form
+        (docs/surrogates.md); ``return_mean_variance`` changes nothing, and a
+        ``compute="bf16"`` model answers from the float32 form."""
+        xr = x.to(self.device, self.dtype)
+        f = self._fitted
+        if ops.gp_mean_grad_native(xr, f.X):
+            cache, pa = self._native_pred_cache(xr.device)
+            return ops.gp_predict_mean_grad_cached(
+                xr.contiguous(), pa, cache[1], cache[2]
+            )[1]
+        _, jac_u = f.predict_mean_grad(self.normalize_query(xr))
+        rg = torch.as_tensor(self.xrg, dtype=jac_u.dtype, device=jac_u.device)
+        return jac_u / rg
+
+    def gradient(self, x) -> np.ndarray:
+        """Gradient of the posterior mean at raw x (P, d) or (d,) ->
+        float64 (P, m, d) in raw input units (see gradient_tensor)."""
+        xin = np.asarray(x, dtype=np.float64)
+        if xin.ndim == 1:
+            xin = xin.reshape(1, self.nInput)
+        jac = self.gradient_tensor(torch.as_tensor(xin))
+        return jac.cpu().numpy().astype(np.float64)
+
 
 class GPRMatern(_GPRBase):
     """Registry name 'gpr' — Matern-5/2 exact GP (reference model.py:1182)."""

@@ -435,6 +435,21 @@ class FittedGP:
                 return self._destandardize(mean_n), mv[:, self.theta.shape[0]:]
             return self._finish_var(Xq, Ks, mean_n)
 
+    def predict_mean_grad(self, Xq: torch.Tensor):
+        """Posterior mean and its gradient in the query point at normalized
+        Xq (P, d) -> (mean (P, m), jac_u (P, m, d)), jac_u[p, b, k] =
+        d mean[p, b] / d Xq[p, k] in unit-box input units and the units of Y.
+
+        The closed form (docs/surrogates.md): float32 GPU fits run the fused
+        kernels of ops/hip/gp_mean_grad.hip, everything else plain torch in
+        the fit's dtype. It reads alpha and theta only, so a ``compute="bf16"``
+        fit answers from the same float32 form."""
+        with _single_threaded_cpu_math(not Xq.is_cuda):
+            return ops.gp_predict_mean_grad(
+                Xq, self.X, self.theta, self.alpha, self.y_mean, self.y_std,
+                self.nu, self.anisotropic,
+            )
+
     def _finish_var(self, Xq, Ks, mean_n):
         sf2 = torch.exp(self.theta[:, 0])
         noise = torch.exp(self.theta[:, -1])

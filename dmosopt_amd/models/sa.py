@@ -1,4 +1,4 @@
-"""Sensitivity analysis on the surrogate (registry 'dgsm', 'fast').
+"""Sensitivity analysis on the surrogate (registry 'dgsm', 'dgsm_grad', 'fast').
 
 Interface parity with reference sa.py (SA_DGSM / SA_FAST: __init__(lo, hi,
 param_names, output_names), analyze(model, num_samples) -> {'S1': {output:
@@ -15,6 +15,7 @@ implemented natively and batched:
 
 from __future__ import annotations
 
+import logging
 import math
 from typing import List
 
@@ -61,6 +62,29 @@ class SA_DGSM:
         v = (grad**2).mean(axis=0)  # (d, m) DGSM measure
         S1s = [v[:, i] for i in range(m)]
         return {"S1": dict(zip(self.output_names, S1s))}
+
+
+class SA_DGSM_Grad(SA_DGSM):
+    """Registry name 'dgsm_grad': the DGSM measure from the surrogate's
+    ANALYTIC input gradient instead of finite differences.
+
+    Same Sobol' base points and seed as 'dgsm' (the inherited ``sample``),
+    same result layout; ``model.gradient(base)`` -> (n, m, d) replaces the
+    (n x 2d)-point surrogate sweep, has no step-size error and does not turn
+    one-sided at the bounds. A model without ``gradient`` takes the
+    finite-difference path of SA_DGSM."""
+
+    def analyze(self, model, num_samples=10000):
+        if not hasattr(model, "gradient"):
+            logger = self.logger or logging.getLogger(__name__)
+            logger.info(
+                f"dgsm_grad: {type(model).__name__} has no gradient(); "
+                "falling back to finite-difference dgsm"
+            )
+            return super().analyze(model, num_samples)
+        jac = np.asarray(model.gradient(self.sample(num_samples)), dtype=np.float64)
+        v = (jac**2).mean(axis=0)  # (m, d) DGSM measure
+        return {"S1": dict(zip(self.output_names, list(v)))}
 
 
 class SA_FAST:

@@ -283,6 +283,44 @@ def gp_predict_mean_var_fused(
     return None
 
 
+#: widest input the gradient kernel takes (16 dimensions per thread)
+GP_MEAN_GRAD_MAX_D = 128
+
+
+def gp_mean_grad_native(Xq, X) -> bool:
+    """The gate of the native mean-gradient path: GPU queries, a float32 GPU
+    fit on the native path, D <= GP_MEAN_GRAD_MAX_D."""
+    return Xq.is_cuda and X.shape[1] <= GP_MEAN_GRAD_MAX_D and native_fp32(X)
+
+
+def gp_predict_mean_grad_cached(Xq, pred_args, q_lb, q_invrg):
+    """Native (mean (P, B), jac (P, B, D)) of float32 queries (raw with q_lb /
+    q_invrg) after the caller has passed gp_mean_grad_native itself; the mean
+    is bitwise gp_predict_mean_cached's."""
+    mean, jac = _native.gp_predict_mean_grad(Xq, *pred_args, q_lb, q_invrg)
+    return mean, jac
+
+
+def gp_predict_mean_grad(
+    Xq, X, theta, alpha, y_mean, y_std, nu, anisotropic, q_lb=None, q_invrg=None
+):
+    """Posterior mean (P, B) and its gradient in the query point (P, B, D),
+    in the units the queries come in (raw with q_lb / q_invrg, unit box
+    without). Float32 GPU tensors with D <= 128 run the fused native kernels
+    (ops/hip/gp_mean_grad.hip); everything else the closed form in plain
+    torch, in the dtype of X."""
+    if gp_mean_grad_native(Xq, X):
+        return gp_predict_mean_grad_cached(
+            Xq.float().contiguous(),
+            gp_pred_args(X, theta, alpha, y_mean, y_std, nu, anisotropic),
+            None if q_lb is None else q_lb.float().contiguous(),
+            None if q_invrg is None else q_invrg.float().contiguous(),
+        )
+    return torch_ref.gp_predict_mean_grad_ref(
+        Xq, X, theta, alpha, y_mean, y_std, nu, anisotropic, q_lb, q_invrg
+    )
+
+
 def sceua_propose(cx, lcs, bl, bu, nps, seed):
     return _native.sceua_propose(cx, lcs, bl, bu, nps, seed)
 

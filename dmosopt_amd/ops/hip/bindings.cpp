@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "launchers.h"
@@ -273,6 +274,45 @@ torch::Tensor gp_predict_mean(torch::Tensor Xq, torch::Tensor X,
   const GpArgs g =
       gp_check_args("gp_predict_mean", X, theta, nu, aniso, q_lb, q_invrg);
   return gp_predict_front(g, Xq, alpha, y_mean, y_std, g.B).out;
+}
+
+// Posterior mean AND its gradient in the query point: {mean (P,B), jac
+// (P,B,D)}, jac[p,b,d] = d mean[p,b] / d Xq[p,d] in the units the queries
+// come in (raw with q_lb / q_invrg, unit box without). The mean is
+// gp_predict_mean's front end; the gradient kernels (gp_mean_grad.hip) read
+// only X, theta and alpha. Their (B, S, P, D) scratch is bounded by slicing P:
+// a query's gradient does not depend on its slice.
+std::vector<torch::Tensor> gp_predict_mean_grad(
+    torch::Tensor Xq, torch::Tensor X, torch::Tensor theta,
+    torch::Tensor alpha, torch::Tensor y_mean, torch::Tensor y_std, double nu,
+    bool aniso, c10::optional<torch::Tensor> q_lb = c10::nullopt,
+    c10::optional<torch::Tensor> q_invrg = c10::nullopt) {
+  const GpArgs g =
+      gp_check_args("gp_predict_mean_grad", X, theta, nu, aniso, q_lb, q_invrg);
+  // the gradient kernel's phase 2 gives a thread 16 of the D dimensions
+  TORCH_CHECK(g.D <= 128, g.fn,
+              ": shape exceeds the launch bounds of the gradient stage "
+              "(D <= 128)");
+  auto f = gp_predict_front(g, Xq, alpha, y_mean, y_std, g.B);
+  const int64_t P = Xq.size(0), S = gp_mean_grad_splits((int)g.N);
+  auto jac = torch::empty({P, g.B, g.D}, X.options());
+  // at most 64 MiB of partials per slice, whole 32-query tiles
+  const int64_t per_query = g.B * S * g.D * (int64_t)sizeof(float);
+  const int64_t slice =
+      std::min(P, std::max<int64_t>(32, ((64LL << 20) / per_query) / 32 * 32));
+  auto part = torch::empty({g.B, S, slice, g.D}, X.options());
+  for (int64_t p0 = 0; p0 < P; p0 += slice) {
+    const int64_t Pc = std::min(slice, P - p0);
+    const int rc = launch_gp_mean_grad(
+        Xq.data_ptr<float>() + p0 * g.D, X.data_ptr<float>(),
+        theta.data_ptr<float>(), alpha.data_ptr<float>(),
+        y_std.data_ptr<float>(), part.data_ptr<float>(),
+        jac.data_ptr<float>() + p0 * g.B * g.D, g.B, Pc, g.N, g.D, g.p, g.nu,
+        aniso ? 1 : 0, g.q_lb, g.q_invrg, cur_stream());
+    TORCH_CHECK(rc == 0, g.fn, ": gradient kernel launch failed: ",
+                hipGetErrorString((hipError_t)rc));
+  }
+  return {f.out, jac};
 }
 
 // Fused mean + variance predict (optimize_mean_variance mode): the front end
@@ -1093,6 +1133,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("Linv"), py::arg("y_mean"), py::arg("y_std"), py::arg("nu"),
         py::arg("aniso"), py::arg("q_lb") = py::none(),
         py::arg("q_invrg") = py::none(), py::arg("var_decimals") = -1);
+  m.def("gp_predict_mean_grad", &gp_predict_mean_grad,
+        "Fused posterior mean (P, B) and its query-point gradient (P, B, D)",
+        py::arg("Xq"), py::arg("X"), py::arg("theta"), py::arg("alpha"),
+        py::arg("y_mean"), py::arg("y_std"), py::arg("nu"), py::arg("aniso"),
+        py::arg("q_lb") = py::none(), py::arg("q_invrg") = py::none());
   m.def("gp_nmll", &gp_nmll, "Fused batched GP NMLL (assemble+chol+solve+reduce)");
   m.def("gp_nmll_grad", &gp_nmll_grad,
         "Fused batched GP NMLL value and analytic gradient");

@@ -54,6 +54,12 @@ int launch_gp_nmll_grad(const float* X, const float* theta, const float* Kinv, c
     const float* nmll, const int* info, float* part, float* grad, int B, int N, int D, int p,
     int nu_code, int aniso, hipStream_t stream);
 
+// ---------------------------------------------------------- gp_mean_grad.hip
+int gp_mean_grad_splits(int N);
+int launch_gp_mean_grad(const float* Xq, const float* X, const float* theta, const float* alpha,
+    const float* y_std, float* part, float* jac, int B, int P, int N, int D, int p, int nu_code,
+    int aniso, const float* q_lb, const float* q_invrg, hipStream_t stream);
+
 // ----------------------------------------------------------- sceua_stage.hip
 void launch_sceua_propose(const float* cx, const int* lcs, const float* bl, const float* bu,
     float* cand, int S, int G, int npg, int nopt, int nps, unsigned long long seed,

@@ -423,3 +423,80 @@ def gp_nmll_grad_ref(X: Tensor, theta: Tensor, y: Tensor, nu, anisotropic: bool,
     nmll = torch.where(bad, torch.full_like(nmll, float("inf")), nmll)
     grad = torch.where(bad[:, None], torch.zeros_like(grad), grad)
     return nmll, grad
+
+
+def gp_predict_mean_grad_ref(Xq: Tensor, X: Tensor, theta: Tensor, alpha: Tensor,
+                             y_mean: Tensor, y_std: Tensor, nu, anisotropic: bool,
+                             q_lb: Optional[Tensor] = None,
+                             q_invrg: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """GP posterior mean and its gradient in the query point, in the dtype of
+    X, on any device.
+
+    Xq (P, D) raw queries with q_lb / q_invrg (u = (Xq - q_lb) * q_invrg),
+    unit-box queries without; X (N, D); theta (B, p) = [log sf2, log ell (1
+    or D), log noise]; alpha (B, N) or (B, N, 1) standardised weights. With
+    r2 = sum_d ((u_d - X_id)/ell_d)^2 and g = dk/d(r2):
+
+        mean[p, b]   = y_mean_b + y_std_b sum_i alpha_bi sf2_b k(r2)
+        jac[p, b, d] = y_std_b q_invrg_d (2/ell_bd^2)
+                       sum_i alpha_bi sf2_b g(r2) (u_d - X_id)
+
+    Both r2 and the factor of the sum are direct differences, one dimension
+    at a time (no (B, P, N, D) temporary). nu = 1/2 has a kink at r = 0: a
+    training point the query sits on contributes 0 to the gradient. Returns
+    (mean (P, B), jac (P, B, D)), jac in the units the queries come in.
+    """
+    import math
+
+    dt = X.dtype
+    P, D = Xq.shape
+    B = theta.shape[0]
+    theta, Xq = theta.to(dt), Xq.to(dt)
+    alpha = alpha.to(dt).reshape(B, -1)
+    y_mean, y_std = y_mean.to(dt).reshape(B), y_std.to(dt).reshape(B)
+    u = Xq if q_lb is None else (Xq - q_lb.to(dt)) * q_invrg.to(dt)
+    sf2 = torch.exp(theta[:, 0])
+    inv_ell = torch.exp(-theta[:, 1 : 1 + D]) if anisotropic else torch.exp(-theta[:, 1:2])
+    inv_ell = inv_ell.expand(B, D)
+    us = u[None, :, :] * inv_ell[:, None, :]  # (B, P, D)
+    xs = X[None, :, :] * inv_ell[:, None, :]  # (B, N, D)
+
+    def s_k(k):
+        return us[:, :, None, k] - xs[:, None, :, k]  # (B, P, N)
+
+    d2 = torch.zeros(B, P, X.shape[0], dtype=dt, device=X.device)
+    for k in range(D):
+        t = s_k(k)
+        d2 += t * t
+    if nu is None or nu == float("inf") or nu == 0.0:
+        c = torch.exp(-0.5 * d2)
+        g = -0.5 * c
+    else:
+        r = torch.sqrt(d2)
+        if nu == 0.5:
+            c = torch.exp(-r)
+            pos = r > 0
+            g = torch.where(pos, -c / (2.0 * torch.where(pos, r, torch.ones_like(r))),
+                            torch.zeros_like(r))
+        elif nu == 1.5:
+            s = math.sqrt(3.0) * r
+            e = torch.exp(-s)
+            c = (1.0 + s) * e
+            g = -1.5 * e
+        elif nu == 2.5:
+            s = math.sqrt(5.0) * r
+            e = torch.exp(-s)
+            c = (1.0 + s + (5.0 / 3.0) * d2) * e
+            g = -(5.0 / 6.0) * (1.0 + s) * e
+        else:
+            raise ValueError(f"Unsupported Matern nu={nu}")
+    sa = sf2[:, None] * alpha  # (B, N)
+    mean = y_mean[None, :] + y_std[None, :] * (c * sa[:, None, :]).sum(dim=2).T
+    w = g * sa[:, None, :]  # (B, P, N)
+    jac = torch.empty(P, B, D, dtype=dt, device=X.device)
+    scale = 2.0 * inv_ell * y_std[:, None]  # (B, D); s_k carries one 1/ell
+    if q_invrg is not None:
+        scale = scale * q_invrg.to(dt)[None, :]
+    for k in range(D):
+        jac[:, :, k] = ((w * s_k(k)).sum(dim=2) * scale[:, k : k + 1]).T
+    return mean, jac

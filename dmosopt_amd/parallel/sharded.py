@@ -92,3 +92,29 @@ class ShardedObjective:
             return full[:, :m], full[:, m:]
         t = torch.as_tensor(np.asarray(out, dtype=np.float64))
         return ctx.all_gather_interleaved(t, P).cpu().numpy()
+
+    @property
+    def gradient(self):
+        """Input gradient of the surrogate mean, raw x (P, d) or (d,) ->
+        float64 (P, m, d): each rank differentiates rows [rank::world] and ONE
+        all_gather moves the (P_shard, m*d) block. Without it __getattr__
+        would hand out the inner model's replicated full-batch call, whose
+        values may differ between ranks on unlike hardware. A property, so
+        that ``hasattr(obj, "gradient")`` answers for the wrapped surrogate
+        (models/sa.py asks): one without ``gradient`` has none here either."""
+        inner_gradient = self._inner.gradient  # AttributeError: no such method
+        ctx = self._ctx
+
+        def gradient(x):
+            x = np.asarray(x, dtype=np.float64)
+            if x.ndim == 1:
+                x = x.reshape(1, -1)
+            P = x.shape[0]
+            pad = (ctx.world - P % ctx.world) % ctx.world
+            xp = np.vstack([x, np.repeat(x[-1:], pad, axis=0)]) if pad else x
+            jac = np.asarray(inner_gradient(xp[ctx.rank :: ctx.world]), dtype=np.float64)
+            t = torch.as_tensor(np.ascontiguousarray(jac.reshape(jac.shape[0], -1)))
+            full = ctx.all_gather_interleaved(t, P).cpu().numpy()
+            return full.reshape(P, *jac.shape[1:])
+
+        return gradient
