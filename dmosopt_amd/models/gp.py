@@ -28,6 +28,7 @@ from dmosopt_amd.models.gp_core import (
     _nmll_bind_enabled,
     batched_nmll,
     batched_nmll_and_grad,
+    stage_graph,
 )
 from dmosopt_amd.models.sceua import sceua_batched
 
@@ -178,9 +179,19 @@ class _GPRBase:
                     nu=self.nu, anisotropic=anisotropic,
                 )
 
+            def stage_runner(sid3, S, G, npg, nps, nopt_, bl_f, bu_f):
+                # the whole CCE stage as one captured launch chain where the
+                # native float32 gate holds (None elsewhere: sceua_batched
+                # then calls nmll_func per stage as before)
+                return stage_graph(
+                    X, rows_for(sid3), self.nu, anisotropic, 1e-10, S, G, npg,
+                    nps, nopt_, bl_f, bu_f,
+                )
+
             bestx, bestf, icall = sceua_batched(
                 nmll_func, bl, bu, nopt, n_streams=m, seed=seed,
                 device=self.device, dtype=self.dtype, logger=None,
+                stage_runner=stage_runner,
             )
             theta = torch.as_tensor(bestx, dtype=self.dtype, device=self.device)
         elif optimizer == "adam":

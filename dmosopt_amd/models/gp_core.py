@@ -201,13 +201,198 @@ class _NmllGraph:
         return self.out.clone()
 
 
+class _StageGraph:
+    """One whole SCE-UA CCE stage as ONE captured linear chain (gfx950):
+    propose -> kernel assembly with the factorization's prologue -> the
+    Cholesky launches, the last one with the NMLL epilogue -> accept;
+    ceil(N/32) + 3 kernel nodes, no memset node, no parallel branch. One
+    replay is one stage: the two SCE-UA kernels read the stage's simplex
+    positions and Philox seed from a per-shuffle schedule in device memory,
+    selected by a device counter that accept advances, so a replay takes no
+    argument. Every buffer the chain touches is owned here and static:
+    the complexes ``cx`` / ``cf``, the candidates ``theta``, the NMLL side
+    buffers, and one int32 control block [step (2) | act (S) | icall (S) |
+    schedule (nspl, nps + 2)] that the host ships in ONE H2D per shuffle.
+    The shuffle boundary (un-partition, global sort, partition, termination
+    pack) runs on the same buffers with two native launches around
+    torch.argsort and one pinned readback. X and the per-row y are bound as
+    in _NmllGraph: copied only when the source object or its version
+    changed."""
+
+    def __init__(self, X, y, nu, anisotropic, jitter, S, G, npg, nps, nopt):
+        dev = X.device
+        N, B, npt, nspl = X.shape[0], 3 * S * G, G * npg, npg
+        self.S, self.G, self.npg, self.nps, self.nopt = S, G, npg, nps, nopt
+        self.nspl = nspl
+        self.args = (nu, anisotropic, jitter)
+        f32 = dict(dtype=torch.float32, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.Xb = X.contiguous().clone()
+        self.yb = y.contiguous().clone()
+        self._bound = {"X": (None, -1), "y": (None, -1)}
+        self.bl = torch.zeros(nopt, **f32)
+        self.bu = torch.zeros(nopt, **f32)
+        self.cx = torch.zeros(S, G, npg, nopt, **f32)
+        self.cf = torch.zeros(S, G, npg, **f32)
+        self.x = torch.zeros(S, npt, nopt, **f32)  # un-partitioned, unsorted
+        self.xf = torch.zeros(S, npt, **f32)
+        self.xs = torch.zeros(S, npt, nopt, **f32)  # sorted population
+        self.xfs = torch.zeros(S, npt, **f32)
+        n_ctl = 2 + 2 * S + nspl * (nps + 2)
+        self.ctl = torch.zeros(n_ctl, **i32)
+        self.step = self.ctl[0:2]
+        self.act = self.ctl[2 : 2 + S]
+        self.icall = self.ctl[2 + S : 2 + 2 * S]
+        self.sched = self.ctl[2 + 2 * S :].view(nspl, nps + 2)
+        self._ctl_host = torch.zeros(n_ctl, dtype=torch.int32).pin_memory()
+        self._ctl_np = self._ctl_host.numpy()
+        self.theta = torch.zeros(B, nopt, **f32)
+        self.K = torch.empty(B, N, N, **f32)
+        self.Z = torch.empty(B, N, **f32)
+        self.logdet = torch.empty(B, **f32)
+        self.info = torch.empty(B, **i32)
+        self.out = torch.empty(B, **f32)
+        self.pack = torch.zeros(S, 2 + 2 * nopt, **f32)
+        self._pack_host = torch.zeros(S, 2 + 2 * nopt).pin_memory()
+        self._pack_np = self._pack_host.numpy()
+        # warm-up and capture run on the zeroed buffers with act = 0: every
+        # index is in range, accept leaves cx / cf alone, and each shuffle
+        # re-ships the control block anyway
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(2):
+                self._queue_stage()
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self._queue_stage()
+
+    def _queue_stage(self):
+        nu, anisotropic, jitter = self.args
+        ops.sceua_propose_sched(
+            self.cx, self.sched, self.step, self.bl, self.bu, self.theta
+        )
+        ops.gp_nmll_into(
+            self.Xb, self.theta, self.yb, self.K, self.Z, self.logdet,
+            self.info, self.out, nu, anisotropic, jitter,
+        )
+        ops.sceua_accept_sched(
+            self.cx, self.cf, self.theta, self.out, self.sched, self.step,
+            self.act, self.icall,
+        )
+
+    def bind(self, X, y, bl, bu):
+        """Once per fit: X, the per-row y (skipped when already bound) and
+        the search bounds."""
+        for slot, buf, src in (("X", self.Xb, X), ("y", self.yb, y)):
+            bound, version = self._bound[slot]
+            if _nmll_bind_enabled() and bound is src and version == src._version:
+                continue
+            buf.copy_(src)
+            self._bound[slot] = (src, src._version)
+        self.bl.copy_(bl)
+        self.bu.copy_(bu)
+
+    def load_population(self, x, xf):
+        """The sorted population (S,npt,nopt) / (S,npt) of the first shuffle,
+        partitioned into the complexes: position p of complex g is row
+        p*G + g."""
+        S, G, npg, nopt = self.S, self.G, self.npg, self.nopt
+        self.xs.copy_(x)
+        self.xfs.copy_(xf)
+        self.cx.copy_(x.view(S, npg, G, nopt).permute(0, 2, 1, 3))
+        self.cf.copy_(xf.view(S, npg, G).permute(0, 2, 1))
+
+    def begin_shuffle(self, act_np, lcs_np, seeds):
+        """Ship one shuffle's control block: counter 0, the active-stream
+        mask, zeroed icall, and per stage the simplex positions (nspl, nps)
+        and the 64-bit seed."""
+        S, nps = self.S, self.nps
+        h = self._ctl_np
+        h[: 2 + 2 * S] = 0
+        h[2 : 2 + S] = act_np
+        sched = h[2 + 2 * S :].reshape(self.nspl, nps + 2)
+        sched[:, :nps] = lcs_np
+        words = sched[:, nps:].view("uint32")
+        for k, seed in enumerate(seeds):
+            words[k, 0] = seed & 0xFFFFFFFF
+            words[k, 1] = seed >> 32
+        self.ctl.copy_(self._ctl_host, non_blocking=True)
+
+    def stage(self):
+        self.graph.replay()
+
+    def end_shuffle(self):
+        """Un-partition, global sort (torch.argsort, exactly the call of
+        sceua.sort_pop: its tie order among failed candidates is part of the
+        trajectory), partition back, and ONE blocking readback of the
+        termination pack (S, 2 + 2 nopt): icall, best f, per-dimension max
+        and min of the population. Afterwards xs / xfs hold the sorted
+        population and cx / cf the next shuffle's complexes."""
+        ops.sceua_unpartition(self.cx, self.cf, self.x, self.xf)
+        order = torch.argsort(self.xf, dim=-1)
+        ops.sceua_partition_pack(
+            self.x, self.xf, order, self.icall, self.xs, self.xfs, self.cx,
+            self.cf, self.pack,
+        )
+        self._pack_host.copy_(self.pack, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        return self._pack_np
+
+
 _nmll_graphs: dict = {}
+_stage_graphs: dict = {}
+
+
+def _evict_graphs_if_full():
+    """Archives grow, so every epoch brings new shapes: both graph caches are
+    dropped together once either holds 8 stale ones."""
+    if len(_nmll_graphs) >= 8 or len(_stage_graphs) >= 8:
+        _nmll_graphs.clear()
+        _stage_graphs.clear()
 
 
 def _nmll_graph_enabled() -> bool:
     import os
 
     return os.environ.get("DMOSOPT_NMLL_GRAPH", "1") == "1"
+
+
+def _sceua_stage_enabled() -> bool:
+    """DMOSOPT_SCEUA_STAGE=0 restores the per-stage propose / NMLL graph /
+    accept path (same-process A/B; outputs are identical either way). Read
+    per fit, not latched."""
+    import os
+
+    return os.environ.get("DMOSOPT_SCEUA_STAGE", "1") == "1"
+
+
+def stage_graph(X, y, nu, anisotropic, jitter, S, G, npg, nps, nopt, bl, bu):
+    """The captured CCE stage for this fit, bound to X (N,d), the per-row
+    targets y (3*S*G, N) and the float32 bounds, or None where the native
+    float32 gate does not hold or DMOSOPT_SCEUA_STAGE / DMOSOPT_NMLL_GRAPH
+    switch it off. Cached on batched_nmll's shape key plus (S, G, npg, nps)."""
+    if not (
+        _sceua_stage_enabled()
+        and _nmll_graph_enabled()
+        and ops.native_fp32(X, y, bl, bu)
+        and y.dim() == 2
+        and y.shape[0] == 3 * S * G
+    ):
+        return None
+    key = (
+        y.shape[0], X.shape[0], X.shape[1], nopt, y.dim(), nu, anisotropic,
+        float(jitter), S, G, npg, nps,
+    )
+    g = _stage_graphs.get(key)
+    if g is None:
+        _evict_graphs_if_full()
+        g = _stage_graphs[key] = _StageGraph(
+            X, y, nu, anisotropic, jitter, S, G, npg, nps, nopt
+        )
+    g.bind(X, y, bl, bu)
+    return g
 
 
 def _nmll_bind_enabled() -> bool:
@@ -259,9 +444,8 @@ def batched_nmll(
                 )
                 g = _nmll_graphs.get(key)
                 if g is None:
-                    if len(_nmll_graphs) >= 8:  # archives grow: drop stale shapes
-                        _nmll_graphs.clear()
-                    g = _nmll_graphs[key] = _NmllGraph(
+                    _evict_graphs_if_full()  # archives grow: drop stale shapes
+                    g =_nmll_graphs[key] = _NmllGraph(
                         X.float(), y.float(), theta.float(), nu, anisotropic, jitter
                     )
                 return g.run(X.float(), y.float(), theta.float())

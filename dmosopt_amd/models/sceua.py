@@ -49,6 +49,19 @@ def _select_simplex(nps: int, npg: int, rng: np.random.Generator) -> np.ndarray:
     return np.asarray(sorted(lcs), dtype=np.int64)
 
 
+def _note_criterion(bestf_now, act_np, criter, criter_change, kstop):
+    """Append each active stream's best f of this shuffle and update its
+    criterion change over the last kstop shuffles, in percent."""
+    for s in range(len(act_np)):
+        if act_np[s]:
+            criter[s].append(float(bestf_now[s]))
+            nl = len(criter[s])
+            if nl >= kstop:
+                num = abs(criter[s][-1] - criter[s][-kstop]) * 100.0
+                den = np.mean(np.abs(criter[s][-kstop:]))
+                criter_change[s] = num / den if den > 0 else 0.0
+
+
 def sceua_batched(
     func: Callable[[torch.Tensor, torch.Tensor], torch.Tensor],
     bl: np.ndarray,
@@ -64,11 +77,20 @@ def sceua_batched(
     logger=None,
     device=None,
     dtype=torch.float64,
+    stage_runner=None,
 ):
     """Run S parallel SCE-UA minimizations with batched evaluation.
 
     func(x (B, nopt), stream (B,) long) -> (B,) objective values.
     Returns (bestx (S, nopt), bestf (S,), icall (S,)) as numpy arrays.
+
+    stage_runner (optional, native float32 stage path only): a callable
+    (sid3, S, G, npg, nps, nopt, bl, bu) -> runner or None. A runner owns the
+    complexes on the device and evaluates func's objective itself: it runs a
+    whole CCE stage per ``stage()`` call and the shuffle boundary per
+    ``end_shuffle()`` (gp_core._StageGraph). The search it performs is the
+    one below, value for value; ``func`` still evaluates the initial
+    population and remains the only interface of every other caller.
     """
     rng = np.random.default_rng(seed)
     device = device or torch.device("cpu")
@@ -129,23 +151,67 @@ def sceua_batched(
     sid_sg = torch.arange(S, device=device).repeat_interleave(G)
     sid3 = torch.cat([sid_sg, sid_sg, sid_sg], dim=0)
 
+    runner = None
+    if use_native_stage and stage_runner is not None:
+        runner = stage_runner(sid3, S, G, npg, nps, nopt, bl_f, bu_f)
+    if runner is not None:
+        runner.load_population(x, xf)
+        # float32 (max - min) / bd as gnrng_of divides it on the device
+        bd_np = bu_t.cpu().numpy() - bl_t.cpu().numpy()
+
+    def draw_simplexes():
+        return np.stack(
+            [_select_simplex(nps, npg, rng) for _ in range(nspl)]
+        ).astype(np.int32)
+
+    def draw_schedule():
+        # one shuffle's draws in the order of the per-stage loop below: the
+        # nspl simplex selections, then the nspl stage seeds
+        lcs_ = draw_simplexes()
+        return lcs_, [int(rng.integers(0, 2**62)) for _ in range(nspl)]
+
     nloop = 0
+    drawn = None
     while True:
         act_np = (icall < maxn) & (gnrng > peps) & (criter_change > pcento)
         if not act_np.any():
             break
         nloop += 1
+
+        if runner is not None:
+            lcs_np, seeds = drawn if drawn is not None else draw_schedule()
+            runner.begin_shuffle(act_np, lcs_np, seeds)
+            for _step in range(nspl):
+                runner.stage()
+            # the next shuffle's schedule, drawn while the device runs this
+            # one (~0.1 ms of host time per shuffle off the serial chain).
+            # Nothing else reads this Generator, so the sequence of draws is
+            # the one above; after the last shuffle one schedule goes unused.
+            drawn = draw_schedule()
+            pk = runner.end_shuffle()  # the ONE blocking readback
+            x, xf = runner.xs, runner.xfs
+            icall += pk[:, 0].astype(np.int64) * act_np
+            # geometric range finished on the host from the exact per-
+            # dimension extrema, in gnrng_of's float32 steps
+            with np.errstate(divide="ignore"):
+                rngs = (pk[:, 2 : 2 + nopt] - pk[:, 2 + nopt :]) / bd_np
+                gnrng = np.exp(
+                    np.log(np.maximum(rngs, np.float32(0.0))).mean(axis=1)
+                ).astype(np.float64)
+            bestf_now = pk[:, 1].astype(np.float64)
+            _note_criterion(bestf_now, act_np, criter, criter_change, kstop)
+            if logger is not None:
+                logger.info(
+                    f"sceua_batched loop {nloop}: bestf={bestf_now}, icall={icall}"
+                )
+            continue
+
         act = torch.as_tensor(act_np, device=device)
 
         # all simplex selections of this shuffle drawn up front: ONE small
         # H2D instead of one per CCE stage (a pageable-memory copy inside
         # the stage loop near-synchronizes the stream and kills pipelining)
-        lcs_all = torch.as_tensor(
-            np.stack([_select_simplex(nps, npg, rng) for _ in range(nspl)]).astype(
-                np.int32
-            ),
-            device=device,
-        )
+        lcs_all = torch.as_tensor(draw_simplexes(), device=device)
 
         # partition: position p of complex g sits at row p*ngs+g
         cx = x.view(S, npg, G, nopt).permute(0, 2, 1, 3).contiguous()  # (S,G,npg,nopt)
@@ -225,14 +291,7 @@ def sceua_batched(
         icall += pack[:S].astype(np.int64) * act_np
         gnrng = pack[S : 2 * S]
         bestf_now = pack[2 * S :]
-        for s in range(S):
-            if act_np[s]:
-                criter[s].append(float(bestf_now[s]))
-                nl = len(criter[s])
-                if nl >= kstop:
-                    num = abs(criter[s][-1] - criter[s][-kstop]) * 100.0
-                    den = np.mean(np.abs(criter[s][-kstop:]))
-                    criter_change[s] = num / den if den > 0 else 0.0
+        _note_criterion(bestf_now, act_np, criter, criter_change, kstop)
         if logger is not None:
             logger.info(
                 f"sceua_batched loop {nloop}: bestf={bestf_now}, icall={icall}"

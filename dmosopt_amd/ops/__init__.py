@@ -329,6 +329,44 @@ def sceua_accept(cx, cf, cand, fall, lcs, act, icall, nps):
     return _native.sceua_accept(cx, cf, cand, fall, lcs, act, icall, nps)
 
 
+def sceua_propose_sched(cx, sched, step, bl, bu, cand):
+    """sceua_propose for the stage ``step[0]`` of the device-side schedule
+    ``sched`` (nspl, nps + 2) int32 — per row the nps simplex positions and
+    the low / high 32-bit words of the stage's Philox seed — written into the
+    caller's ``cand`` (3, S*G, nopt). Posts ``step[0] + 1`` in ``step[1]``."""
+    _native.sceua_propose_sched(cx, sched, step, bl, bu, cand)
+
+
+def sceua_accept_sched(cx, cf, cand, fall, sched, step, act, icall):
+    """sceua_accept for the stage ``step[1] - 1`` of the device-side schedule;
+    its last act advances ``step[0]`` to ``step[1]``."""
+    _native.sceua_accept_sched(cx, cf, cand, fall, sched, step, act, icall)
+
+
+def sceua_unpartition(cx, cf, x, xf):
+    """Complexes (S,G,npg,.) -> population (S,npt,.), row p*G + g = position
+    p of complex g, into the caller's ``x`` / ``xf``."""
+    _native.sceua_unpartition(cx, cf, x, xf)
+
+
+def sceua_partition_pack(x, xf, order, icall, xs, xfs, cx, cf, pack):
+    """Population gathered by ``order`` (S,npt) int64 -> ``xs`` / ``xfs``, its
+    partition into the complexes ``cx`` / ``cf``, and the termination pack
+    (S, 2 + 2 nopt) float32: icall, best f, per-dimension max, then min."""
+    _native.sceua_partition_pack(x, xf, order, icall, xs, xfs, cx, cf, pack)
+
+
+def gp_nmll_into(X, theta, y, K, Z, logdet, info, out, nu, anisotropic, jitter):
+    """gp_nmll_fused's values, bit for bit, into caller-owned float32 buffers
+    K (B,N,N), Z (B,N), logdet (B,), out (B,) and int32 info (B,): no
+    allocation, and where the look-ahead fused-solve route applies no fill,
+    copy or reduce launch either. Native only."""
+    _native.gp_nmll_into(
+        X, theta, y, K, Z, logdet, info, out, _nu_arg(nu), bool(anisotropic),
+        float(jitter),
+    )
+
+
 def gp_nmll_fused(X, theta, y, nu, anisotropic, jitter):
     """Fused batched GP NMLL (assemble + Cholesky + solve + reduce) in one
     extension call; None if the native path does not apply."""

@@ -108,21 +108,30 @@ static void gp_check_query(const GpArgs& g, const torch::Tensor& Xq,
 // `symmetric` (0 cross, 1 train, 2 direct-difference cross). grid.z carries B
 // and grid.y / grid.x the 32-wide tiles; the kernel indexes its inputs with
 // ints and stages two 32 x (D|1) slabs in the default 64 KiB of LDS.
-static torch::Tensor gp_assemble(const GpArgs& g, const torch::Tensor& Xq,
-                                 int nu, int form, float jitter) {
-  const int64_t P = Xq.size(0);
+static void gp_check_assemble(const GpArgs& g, int64_t P) {
   TORCH_CHECK(g.B <= 65535 && (g.N + 31) / 32 <= 65535 &&
                   (P + 31) / 32 <= 65535 && P * g.D < (1LL << 31) &&
                   g.N * g.D < (1LL << 31) && g.D <= 254,
               g.fn, ": shape exceeds the launch bounds (B <= 65535, N and P "
               "<= 2097120, D <= 254)");
-  auto K = torch::empty({g.B, P, g.N}, g.X.options());
+}
+
+static void gp_assemble_into(const GpArgs& g, const torch::Tensor& Xq, int nu,
+                             int form, float jitter, torch::Tensor& K) {
+  const int64_t P = Xq.size(0);
+  gp_check_assemble(g, P);
   launch_matern_assemble_affine(
       Xq.data_ptr<float>(), g.X.data_ptr<float>(), g.theta.data_ptr<float>(),
       K.data_ptr<float>(), g.B, P, g.N, g.D, g.p, jitter, nu, g.aniso ? 1 : 0,
       form, form == 1 ? nullptr : g.q_lb, form == 1 ? nullptr : g.q_invrg,
       cur_stream());
   gp_check_launch(g.fn, "kernel assembly");
+}
+
+static torch::Tensor gp_assemble(const GpArgs& g, const torch::Tensor& Xq,
+                                 int nu, int form, float jitter) {
+  auto K = torch::empty({g.B, Xq.size(0), g.N}, g.X.options());
+  gp_assemble_into(g, Xq, nu, form, jitter, K);
   return K;
 }
 
@@ -140,26 +149,18 @@ torch::Tensor matern_cross(torch::Tensor Xq, torch::Tensor X,
   return gp_assemble(g, Xq, g.nu, 0, 0.f);
 }
 
-// NMLL value pipeline: kernel assembly -> batched Cholesky with the forward
-// solve of y -> reduction, all queued from ONE python call (the per-stage
-// torch dispatch chain was ~40% of the SCE-UA fit's host time). K holds the
-// factor L, Z = L^-1 y (B,N,1), info the factorization flags, out the NMLL
-// (B,), +inf where the factorization failed.
-struct NmllPipeline {
-  torch::Tensor K, Z, info, out;
-};
+static float gp_nmll_const(int N) {
+  return 0.5f * (float)N * 1.8378770664093453f;  // N/2 log(2*pi)
+}
 
-static NmllPipeline gp_nmll_pipeline(const GpArgs& g, const torch::Tensor& y,
-                                     double jitter) {
+// Back half of the NMLL value pipeline on initialised buffers (K assembled,
+// Z = y rows, info = 0): factor with the fused forward solve, or factor and
+// solve separately where the fused route does not apply, then the reduction.
+static void gp_nmll_factor_reduce(const GpArgs& g, torch::Tensor& K,
+                                  torch::Tensor& logdet, torch::Tensor& info,
+                                  torch::Tensor& Z, torch::Tensor& out) {
   auto stream = cur_stream();
   const int B = g.B, N = g.N;
-  auto K = gp_assemble(g, g.X, g.nu, 1, (float)jitter);
-  auto logdet = torch::empty({g.B}, g.X.options());
-  auto info = torch::zeros({g.B}, g.X.options().dtype(torch::kInt32));
-  torch::Tensor Z = (y.dim() == 1)
-                        ? y.unsqueeze(0).expand({g.B, g.N}).contiguous()
-                        : y.contiguous().clone();
-  Z = Z.view({g.B, g.N, 1});
   // fused factor+solve: the rhs rides the multik launch chain (panel solves
   // its 32-entry segment, the SYRK's diagonal tiles apply the trailing
   // update) — no separate ~61 us serial TRSV kernel per NMLL
@@ -172,13 +173,85 @@ static NmllPipeline gp_nmll_pipeline(const GpArgs& g, const torch::Tensor& y,
     launch_forward_solve_batched(K.data_ptr<float>(), Z.data_ptr<float>(), B,
                                  N, 1, stream);
   }
-  auto out = torch::empty({g.B}, g.X.options());
-  const float c = 0.5f * (float)N * 1.8378770664093453f;  // log(2*pi)
   launch_nmll_reduce(Z.data_ptr<float>(), logdet.data_ptr<float>(),
-                     info.data_ptr<int>(), out.data_ptr<float>(), B, N, c,
-                     stream);
+                     info.data_ptr<int>(), out.data_ptr<float>(), B, N,
+                     gp_nmll_const(N), stream);
   gp_check_launch(g.fn, "NMLL pipeline");
+}
+
+// NMLL value pipeline: kernel assembly -> batched Cholesky with the forward
+// solve of y -> reduction, all queued from ONE python call (the per-stage
+// torch dispatch chain was ~40% of the SCE-UA fit's host time). K holds the
+// factor L, Z = L^-1 y (B,N,1), info the factorization flags, out the NMLL
+// (B,), +inf where the factorization failed.
+struct NmllPipeline {
+  torch::Tensor K, Z, info, out;
+};
+
+static NmllPipeline gp_nmll_pipeline(const GpArgs& g, const torch::Tensor& y,
+                                     double jitter) {
+  auto K = gp_assemble(g, g.X, g.nu, 1, (float)jitter);
+  auto logdet = torch::empty({g.B}, g.X.options());
+  auto info = torch::zeros({g.B}, g.X.options().dtype(torch::kInt32));
+  // the solve runs in place on Z. With B = 1 the expanded view of a shared y
+  // is already contiguous, contiguous() hands back y's own storage, and the
+  // caller's y would come back as L^-1 y: that case needs its own copy.
+  torch::Tensor Z = (y.dim() == 1)
+                        ? (g.B == 1 ? y.unsqueeze(0).clone()
+                                    : y.unsqueeze(0).expand({g.B, g.N}).contiguous())
+                        : y.contiguous().clone();
+  Z = Z.view({g.B, g.N, 1});
+  auto out = torch::empty({g.B}, g.X.options());
+  gp_nmll_factor_reduce(g, K, logdet, info, Z, out);
   return {K, Z, info, out};
+}
+
+// The same NMLL values (bit for bit) into CALLER-OWNED buffers K (B,N,N),
+// Z (B,N), logdet (B,), info (B,) int32, out (B,): no allocation, so a
+// captured graph of it owns nothing behind the caller's back. Where the
+// look-ahead fused-solve route applies (N > 32, B <= 48, no switch against
+// it) the prologue rides the assemble launch and the reduction the last step
+// launch: ceil(N/32) + 1 launches, none of them a fill, a copy or a reduce.
+// Elsewhere: today's launches on the caller's buffers. The buffers' previous
+// contents are never read.
+void gp_nmll_into(torch::Tensor X, torch::Tensor theta, torch::Tensor y,
+                  torch::Tensor K, torch::Tensor Z, torch::Tensor logdet,
+                  torch::Tensor info, torch::Tensor out, double nu, bool aniso,
+                  double jitter) {
+  const GpArgs g = gp_check_args("gp_nmll_into", X, theta, nu, aniso);
+  gp_check_targets(g, y);
+  gp_check_f32(g.fn, "K", K);
+  gp_check_f32(g.fn, "Z", Z);
+  gp_check_f32(g.fn, "logdet", logdet);
+  gp_check_f32(g.fn, "out", out);
+  TORCH_CHECK(info.is_cuda() && info.is_contiguous() &&
+                  info.scalar_type() == torch::kInt32,
+              g.fn, ": info must be a contiguous int32 GPU tensor");
+  TORCH_CHECK(K.numel() == g.B * g.N * g.N && Z.numel() == g.B * g.N &&
+                  logdet.numel() == g.B && info.numel() == g.B &&
+                  out.numel() == g.B,
+              g.fn, ": K (B,N,N), Z (B,N), logdet/info/out (B,) required");
+  const int B = g.B, N = g.N;
+  if (cholesky_nmll_chain_applies(B, N)) {
+    gp_check_assemble(g, g.N);
+    auto stream = cur_stream();
+    launch_matern_train_prologue(
+        X.data_ptr<float>(), theta.data_ptr<float>(), K.data_ptr<float>(), B,
+        N, g.D, g.p, (float)jitter, g.nu, aniso ? 1 : 0, y.data_ptr<float>(),
+        y.dim() == 1 ? 0 : N, Z.data_ptr<float>(), logdet.data_ptr<float>(),
+        info.data_ptr<int>(), stream);
+    launch_cholesky_nmll_chain(K.data_ptr<float>(), logdet.data_ptr<float>(),
+                               info.data_ptr<int>(), Z.data_ptr<float>(),
+                               out.data_ptr<float>(), B, N, gp_nmll_const(N),
+                               stream);
+    gp_check_launch(g.fn, "NMLL pipeline");
+    return;
+  }
+  gp_assemble_into(g, g.X, g.nu, 1, (float)jitter, K);
+  info.zero_();
+  Z.view({g.B, g.N}).copy_(y.dim() == 1 ? y.unsqueeze(0).expand({g.B, g.N})
+                                        : y);
+  gp_nmll_factor_reduce(g, K, logdet, info, Z, out);
 }
 
 // Fused GP negative log marginal likelihood for a batch of theta.
@@ -510,6 +583,123 @@ bool sceua_accept(torch::Tensor cx, torch::Tensor cf, torch::Tensor cand,
                              lcs.data_ptr<int>(), act.data_ptr<int>(),
                              icall.data_ptr<int>(), S, G, npg, nopt, (int)nps,
                              cur_stream()) == 0;
+}
+
+// Device-schedule forms of the two stage kernels and the shuffle-boundary
+// kernels (sceua_stage.hip). They write caller-owned buffers only, so a
+// captured stage allocates nothing.
+struct SceuaDims {
+  int S, G, npg, nopt, nps, nspl;
+};
+
+static void sceua_check(const char* fn, const char* name,
+                        const torch::Tensor& t, torch::ScalarType dt,
+                        int64_t numel) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == dt &&
+                  t.numel() == numel,
+              fn, ": ", name, " has the wrong device, layout, dtype or size");
+}
+
+static SceuaDims sceua_check_stage(const char* fn, const torch::Tensor& cx,
+                                   const torch::Tensor& sched,
+                                   const torch::Tensor& step,
+                                   const torch::Tensor& cand) {
+  TORCH_CHECK(cx.dim() == 4 && sched.dim() == 2 && sched.size(1) >= 3, fn,
+              ": cx (S,G,npg,nopt) and sched (nspl, nps + 2) required");
+  const SceuaDims d = {(int)cx.size(0), (int)cx.size(1), (int)cx.size(2),
+                       (int)cx.size(3), (int)sched.size(1) - 2,
+                       (int)sched.size(0)};
+  sceua_check(fn, "cx", cx, torch::kFloat32, cx.numel());
+  sceua_check(fn, "sched", sched, torch::kInt32, sched.numel());
+  sceua_check(fn, "step", step, torch::kInt32, 2);
+  sceua_check(fn, "cand", cand, torch::kFloat32,
+              3LL * d.S * d.G * d.nopt);
+  TORCH_CHECK(d.nspl >= 1 && d.nps >= 2 && d.nps <= d.npg, fn,
+              ": schedule shape does not match the complexes");
+  return d;
+}
+
+void sceua_propose_sched(torch::Tensor cx, torch::Tensor sched,
+                         torch::Tensor step, torch::Tensor bl,
+                         torch::Tensor bu, torch::Tensor cand) {
+  const char* fn = "sceua_propose_sched";
+  const SceuaDims d = sceua_check_stage(fn, cx, sched, step, cand);
+  sceua_check(fn, "bl", bl, torch::kFloat32, d.nopt);
+  sceua_check(fn, "bu", bu, torch::kFloat32, d.nopt);
+  launch_sceua_propose_sched(cx.data_ptr<float>(), sched.data_ptr<int>(),
+                             step.data_ptr<int>(), bl.data_ptr<float>(),
+                             bu.data_ptr<float>(), cand.data_ptr<float>(),
+                             d.S, d.G, d.npg, d.nopt, d.nps, d.nspl,
+                             cur_stream());
+  gp_check_launch(fn, "propose");
+}
+
+void sceua_accept_sched(torch::Tensor cx, torch::Tensor cf,
+                        torch::Tensor cand, torch::Tensor fall,
+                        torch::Tensor sched, torch::Tensor step,
+                        torch::Tensor act, torch::Tensor icall) {
+  const char* fn = "sceua_accept_sched";
+  const SceuaDims d = sceua_check_stage(fn, cx, sched, step, cand);
+  sceua_check(fn, "cf", cf, torch::kFloat32, (int64_t)d.S * d.G * d.npg);
+  sceua_check(fn, "fall", fall, torch::kFloat32, 3LL * d.S * d.G);
+  sceua_check(fn, "act", act, torch::kInt32, d.S);
+  sceua_check(fn, "icall", icall, torch::kInt32, d.S);
+  const int rc = launch_sceua_accept_sched(
+      cx.data_ptr<float>(), cf.data_ptr<float>(), cand.data_ptr<float>(),
+      fall.data_ptr<float>(), sched.data_ptr<int>(), step.data_ptr<int>(),
+      act.data_ptr<int>(), icall.data_ptr<int>(), d.S, d.G, d.npg, d.nopt,
+      d.nps, d.nspl, cur_stream());
+  TORCH_CHECK(rc == 0, fn, ": a complex does not fit the kernel's LDS");
+  gp_check_launch(fn, "accept");
+}
+
+// (S,G,npg,.) complexes -> (S,npt,.) population, row p*G + g = position p of
+// complex g.
+void sceua_unpartition(torch::Tensor cx, torch::Tensor cf, torch::Tensor x,
+                       torch::Tensor xf) {
+  const char* fn = "sceua_unpartition";
+  TORCH_CHECK(cx.dim() == 4, fn, ": cx (S,G,npg,nopt) required");
+  const int S = cx.size(0), G = cx.size(1), npg = cx.size(2),
+            nopt = cx.size(3);
+  sceua_check(fn, "cx", cx, torch::kFloat32, cx.numel());
+  sceua_check(fn, "cf", cf, torch::kFloat32, (int64_t)S * G * npg);
+  sceua_check(fn, "x", x, torch::kFloat32, cx.numel());
+  sceua_check(fn, "xf", xf, torch::kFloat32, (int64_t)S * G * npg);
+  launch_sceua_unpartition(cx.data_ptr<float>(), cf.data_ptr<float>(),
+                           x.data_ptr<float>(), xf.data_ptr<float>(), S, G,
+                           npg, nopt, cur_stream());
+  gp_check_launch(fn, "un-partition");
+}
+
+// Population gathered by `order` (S,npt) int64 -> sorted population (xs,
+// xfs), its partition into complexes (cx, cf) and the termination pack
+// (S, 2 + 2 nopt): icall, best f, per-dimension max, per-dimension min.
+void sceua_partition_pack(torch::Tensor x, torch::Tensor xf,
+                          torch::Tensor order, torch::Tensor icall,
+                          torch::Tensor xs, torch::Tensor xfs,
+                          torch::Tensor cx, torch::Tensor cf,
+                          torch::Tensor pack) {
+  const char* fn = "sceua_partition_pack";
+  TORCH_CHECK(cx.dim() == 4, fn, ": cx (S,G,npg,nopt) required");
+  const int S = cx.size(0), G = cx.size(1), npg = cx.size(2),
+            nopt = cx.size(3);
+  const int64_t rows = (int64_t)S * G * npg;
+  sceua_check(fn, "x", x, torch::kFloat32, rows * nopt);
+  sceua_check(fn, "xf", xf, torch::kFloat32, rows);
+  sceua_check(fn, "order", order, torch::kInt64, rows);
+  sceua_check(fn, "icall", icall, torch::kInt32, S);
+  sceua_check(fn, "xs", xs, torch::kFloat32, rows * nopt);
+  sceua_check(fn, "xfs", xfs, torch::kFloat32, rows);
+  sceua_check(fn, "cx", cx, torch::kFloat32, rows * nopt);
+  sceua_check(fn, "cf", cf, torch::kFloat32, rows);
+  sceua_check(fn, "pack", pack, torch::kFloat32, (int64_t)S * (2 + 2 * nopt));
+  launch_sceua_partition_pack(
+      x.data_ptr<float>(), xf.data_ptr<float>(),
+      (const long long*)order.data_ptr<int64_t>(), icall.data_ptr<int>(),
+      xs.data_ptr<float>(), xfs.data_ptr<float>(), cx.data_ptr<float>(),
+      cf.data_ptr<float>(), pack.data_ptr<float>(), S, G, npg, nopt,
+      cur_stream());
+  gp_check_launch(fn, "partition");
 }
 
 std::vector<torch::Tensor> cholesky_batched_(torch::Tensor A) {
@@ -1120,6 +1310,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("survivor_count", &survivor_count);
   m.def("sceua_propose", &sceua_propose);
   m.def("sceua_accept", &sceua_accept);
+  m.def("sceua_propose_sched", &sceua_propose_sched,
+        "sceua_propose reading its stage's simplex and seed from device memory");
+  m.def("sceua_accept_sched", &sceua_accept_sched,
+        "sceua_accept reading its stage's simplex from device memory");
+  m.def("sceua_unpartition", &sceua_unpartition);
+  m.def("sceua_partition_pack", &sceua_partition_pack);
+  m.def("gp_nmll_into", &gp_nmll_into,
+        "gp_nmll into caller-owned K, Z, logdet, info, out (no allocation)");
   m.def("nsga2_select", &nsga2_select, "Fused survivor selection (cat+rank+crowding+sort+gather)");
   m.def("nsga2_select_acc", &nsga2_select_acc);
   m.def("generation_spawn", &generation_spawn, py::arg("population"), py::arg("rank"), py::arg("poolsize"), py::arg("p_sel"), py::arg("seed_t"), py::arg("ci"), py::arg("mi"), py::arg("p1"), py::arg("p2"), py::arg("im"), py::arg("di_c"), py::arg("di_m"), py::arg("lo"), py::arg("hi"), py::arg("mutation_rate"), py::arg("seed_sbx"), py::arg("seed_mut"), py::arg("rank_sorted") = false);

@@ -657,6 +657,37 @@ __global__ __launch_bounds__(CHOL_SYRK_TPB) void chol_syrk_kernel(
                       rhs ? rhs + (long long)b * N : nullptr, Pi, Pj);
 }
 
+// Final NMLL assembly: out = 0.5 * sum(z^2) + half_logdet + c, inf where the
+// factorization failed or the value is non-finite — fuses the (z*z).sum +
+// scalar-combine + masking chain (a handful of torch dispatches per SCE-UA
+// stage). ONE body for nmll_reduce_kernel and for the epilogue of the last
+// chol_step_kernel launch, with explicit fmaf, so both give the same bits:
+// a strided partial per thread over the first NMLL_REDUCE_TPB threads, then
+// the tree. Every thread of the block must call it (barriers); threads
+// beyond NMLL_REDUCE_TPB only keep the barriers company. part: LDS,
+// NMLL_REDUCE_TPB floats.
+#define NMLL_REDUCE_TPB 256
+__device__ __forceinline__ void nmll_reduce_body(
+    const float* z, const float* half_logdet_b, const int* info_b,
+    float* out_b, int N, float c, float* part) {
+  const int tid = threadIdx.x;
+  if (tid < NMLL_REDUCE_TPB) {
+    float acc = 0.f;
+    for (int i = tid; i < N; i += NMLL_REDUCE_TPB) acc = fmaf(z[i], z[i], acc);
+    part[tid] = acc;
+  }
+  __syncthreads();
+  for (int off = NMLL_REDUCE_TPB >> 1; off > 0; off >>= 1) {
+    if (tid < off) part[tid] += part[tid + off];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    float v = fmaf(0.5f, part[0], *half_logdet_b) + c;
+    if (*info_b != 0 || !isfinite(v)) v = INFINITY;
+    *out_b = v;
+  }
+}
+
 // ------------------------------------------------------ look-ahead step
 // One launch per panel step s >= 1 (k0 = 32 s), grid (B, 1 + tiles); the
 // kernel boundary is the only synchronization (one stream, no events, no
@@ -677,7 +708,8 @@ __global__ __launch_bounds__(CHOL_SYRK_TPB) void chol_syrk_kernel(
 // role), keeping the static LDS at the panel's ~55 KB + 4 KB for Lj.
 __global__ __launch_bounds__(CHOL_PANEL_TPB) void chol_step_kernel(
     float* __restrict__ A, float* __restrict__ logdet, int* __restrict__ info,
-    int N, int k0, float* __restrict__ rhs) {
+    int N, int k0, float* __restrict__ rhs, float* __restrict__ nmll_out,
+    float nmll_c) {
   __shared__ float S[CHOL_BS][CHOL_BS + 1];
   __shared__ float colbuf[CHOL_GROUP_COLS][CHOL_BS];
   __shared__ float P[CHOL_PANEL_TPB][CHOL_BS + 1];
@@ -690,6 +722,17 @@ __global__ __launch_bounds__(CHOL_PANEL_TPB) void chol_step_kernel(
   if (blockIdx.y == 0) {
     chol_panel_body<true>(Ab, logdet + b, info + b, N, k0, rhs_b, S, colbuf,
                           P, Lj);
+    if (nmll_out != nullptr) {
+      // NMLL epilogue of the LAST step (no role-B blocks, no trailing rows):
+      // wave 0 has just solved the final rhs segment, so Z[b], logdet[b] and
+      // info[b] are final and this block reduces them itself. The barrier
+      // and fence publish wave 0's global writes to the other waves; the
+      // partials reuse the (idle) TRSM buffer.
+      __syncthreads();
+      __threadfence_block();
+      nmll_reduce_body(rhs_b, logdet + b, info + b, nmll_out + b, N, nmll_c,
+                       &P[0][0]);
+    }
   } else {
     float(*Pi)[CHOL_BS] = (float(*)[CHOL_BS]) & P[0][0];
     float(*Pj)[CHOL_BS] = Pi + SYRK_TS;
@@ -817,37 +860,21 @@ __global__ void backward_solve_batched_kernel(const float* __restrict__ L,
   }
 }
 
-// Final NMLL assembly: out[b] = 0.5 * sum(Z_b^2) + half_logdet[b] + c,
-// inf where the factorization failed or the value is non-finite — fuses the
-// (z*z).sum + scalar-combine + masking chain (a handful of torch dispatches
-// per SCE-UA stage) into one launch.
 __global__ void nmll_reduce_kernel(const float* __restrict__ Z,
                                    const float* __restrict__ half_logdet,
                                    const int* __restrict__ info,
                                    float* __restrict__ out, int N, float c) {
-  __shared__ float part[256];
+  __shared__ float part[NMLL_REDUCE_TPB];
   const int b = blockIdx.x;
-  const float* z = Z + (long long)b * N;
-  float acc = 0.f;
-  for (int i = threadIdx.x; i < N; i += blockDim.x) acc += z[i] * z[i];
-  part[threadIdx.x] = acc;
-  __syncthreads();
-  for (int off = blockDim.x >> 1; off > 0; off >>= 1) {
-    if (threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    float v = 0.5f * part[0] + half_logdet[b] + c;
-    if (info[b] != 0 || !isfinite(v)) v = INFINITY;
-    out[b] = v;
-  }
+  nmll_reduce_body(Z + (long long)b * N, half_logdet + b, info + b, out + b, N,
+                   c, part);
 }
 
 extern "C" void launch_nmll_reduce(const float* Z, const float* half_logdet,
                                    const int* info, float* out, int B, int N,
                                    float c, hipStream_t stream) {
-  hipLaunchKernelGGL(nmll_reduce_kernel, dim3(B), dim3(256), 0, stream, Z,
-                     half_logdet, info, out, N, c);
+  hipLaunchKernelGGL(nmll_reduce_kernel, dim3(B), dim3(NMLL_REDUCE_TPB), 0,
+                     stream, Z, half_logdet, info, out, N, c);
 }
 
 __global__ void zero_f32_kernel(float* __restrict__ p, int n) {
@@ -913,16 +940,21 @@ static void chol_multik_classic(float* A, float* logdet, int* info,
   }
 }
 
+// nmll_out != nullptr (needs rhs and N > 32): the LAST step launch also
+// reduces the NMLL into nmll_out (B,) — see chol_step_kernel.
 static void chol_multik_lookahead(float* A, float* logdet, int* info,
                                   float* rhs, int B, int N,
-                                  hipStream_t stream) {
+                                  hipStream_t stream,
+                                  float* nmll_out = nullptr,
+                                  float nmll_c = 0.f) {
   launch_chol_panel(A, logdet, info, rhs, B, N, 0, stream);
   for (int k0 = CHOL_BS; k0 < N; k0 += CHOL_BS) {
     // role B covers rows/columns >= k0 + 32; none left on the last steps
     const int pairs = chol_tile_pairs(N, k0 + CHOL_BS);
+    const bool last = k0 + CHOL_BS >= N;
     hipLaunchKernelGGL(chol_step_kernel, dim3(B, 1 + pairs),
                        dim3(CHOL_PANEL_TPB), 0, stream, A, logdet, info, N,
-                       k0, rhs);
+                       k0, rhs, last ? nmll_out : (float*)nullptr, nmll_c);
   }
 }
 
@@ -972,18 +1004,40 @@ extern "C" void launch_cholesky_multik_bf16(float* A, float* logdet,
 // apply (DMOSOPT_CHOL_MODE=single, DMOSOPT_CHOL_FUSED_SOLVE=0, a single
 // panel, or a batch large enough for the one-block-per-matrix kernel); the
 // caller then factors and solves separately.
-extern "C" int launch_cholesky_fused_solve(float* A, float* logdet,
-                                           int* info, float* rhs, int B,
-                                           int N, hipStream_t stream) {
+static inline bool chol_fused_solve_applies(int B, int N) {
   static int ok = -1;
   if (ok < 0) {
     const char* m = getenv("DMOSOPT_CHOL_MODE");
     const char* f = getenv("DMOSOPT_CHOL_FUSED_SOLVE");
     ok = ((m && m[0] == 's') || (f && f[0] == '0')) ? 0 : 1;
   }
-  if (!ok || N <= CHOL_BS || B > CHOL_MULTIK_MAX_B) return -1;
+  return ok && N > CHOL_BS && B <= CHOL_MULTIK_MAX_B;
+}
+
+extern "C" int launch_cholesky_fused_solve(float* A, float* logdet,
+                                           int* info, float* rhs, int B,
+                                           int N, hipStream_t stream) {
+  if (!chol_fused_solve_applies(B, N)) return -1;
   launch_cholesky_multik(A, logdet, info, rhs, B, N, stream);
   return 0;
+}
+
+// 1 when launch_cholesky_fused_solve would take the look-ahead multik route
+// for this shape: the route whose launch chain can carry the NMLL prologue
+// and epilogue (launch_cholesky_nmll_chain).
+extern "C" int cholesky_nmll_chain_applies(int B, int N) {
+  return chol_fused_solve_applies(B, N) && chol_lookahead_default();
+}
+
+// Look-ahead factor + fused forward solve + NMLL, ceil(N/32) launches and
+// nothing else: the caller's assemble launch has already set rhs = y,
+// logdet = 0 and info = 0 (matern.hip's prologue variant), and the last step
+// launch writes out (B,). Only where cholesky_nmll_chain_applies(B, N).
+extern "C" void launch_cholesky_nmll_chain(float* A, float* logdet, int* info,
+                                           float* rhs, float* out, int B,
+                                           int N, float c,
+                                           hipStream_t stream) {
+  chol_multik_lookahead(A, logdet, info, rhs, B, N, stream, out, c);
 }
 
 extern "C" void launch_cholesky_batched(float* A, float* logdet, int* info,

@@ -15,6 +15,10 @@ extern "C" {
 void launch_matern_assemble_affine(const float* Xq, const float* X, const float* theta, float* K,
     int B, int P, int N, int D, int theta_stride, float jitter, int nu_code, int aniso,
     int symmetric, const float* q_lb, const float* q_invrg, hipStream_t stream);
+// train form whose launch also sets Z = y rows (y_stride 0 or N), logdet = 0, info = 0
+void launch_matern_train_prologue(const float* X, const float* theta, float* K, int B, int N, int D,
+    int theta_stride, float jitter, int nu_code, int aniso, const float* y, int y_stride, float* Z,
+    float* logdet, int* info, hipStream_t stream);
 void launch_gp_mean_gemv(const float* Ks, const float* alpha, const float* y_mean,
     const float* y_std, float* out, int B, int P, int N, int ldo, hipStream_t stream);
 
@@ -28,6 +32,11 @@ void launch_cholesky_multik_bf16(float* A, float* logdet, int* info, int B, int 
 // returns nonzero, launching nothing, when the fused path does not apply
 int launch_cholesky_fused_solve(float* A, float* logdet, int* info, float* rhs, int B, int N,
     hipStream_t stream);
+// look-ahead factor + fused solve + NMLL in ceil(N/32) launches, after the prologue assemble; only
+// where cholesky_nmll_chain_applies (the shapes and switches of the look-ahead fused-solve route)
+int cholesky_nmll_chain_applies(int B, int N);
+void launch_cholesky_nmll_chain(float* A, float* logdet, int* info, float* rhs, float* out, int B,
+    int N, float c, hipStream_t stream);
 void launch_cholesky_batched(float* A, float* logdet, int* info, int B, int N, hipStream_t stream);
 void launch_forward_solve_batched(const float* L, float* Y, int B, int N, int R, hipStream_t stream);
 void launch_backward_solve_batched(const float* L, float* Y, int B, int N, int R,
@@ -66,6 +75,20 @@ void launch_sceua_propose(const float* cx, const int* lcs, const float* bl, cons
     hipStream_t stream);
 int launch_sceua_accept(float* cx, float* cf, const float* cand, const float* fall, const int* lcs,
     const int* act, int* icall, int S, int G, int npg, int nopt, int nps, hipStream_t stream);
+// device-schedule forms: sched (nspl, nps + 2) int32 rows of simplex positions + seed words,
+// step (2,) int32 stage counter and hand-over word
+void launch_sceua_propose_sched(const float* cx, const int* sched, int* step, const float* bl,
+    const float* bu, float* cand, int S, int G, int npg, int nopt, int nps, int nspl,
+    hipStream_t stream);
+int launch_sceua_accept_sched(float* cx, float* cf, const float* cand, const float* fall,
+    const int* sched, int* step, const int* act, int* icall, int S, int G, int npg, int nopt,
+    int nps, int nspl, hipStream_t stream);
+// shuffle boundary: (S,G,npg,.) -> (S,npt,.), and back by a sort order with the termination pack
+void launch_sceua_unpartition(const float* cx, const float* cf, float* x, float* xf, int S, int G,
+    int npg, int nopt, hipStream_t stream);
+void launch_sceua_partition_pack(const float* x, const float* xf, const long long* order,
+    const int* icall, float* xs, float* xfs, float* cx, float* cf, float* pack, int S, int G,
+    int npg, int nopt, hipStream_t stream);
 
 // ---------------------------------------------------------------- pareto.hip
 void launch_peel_single_block(const int* D, int* rank, int N, int m, hipStream_t stream);

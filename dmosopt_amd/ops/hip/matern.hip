@@ -43,7 +43,22 @@ __device__ __forceinline__ float matern_transform(float d2) {
 // much — the posterior VARIANCE under nu = 1/2, whose kernel has an
 // infinite slope in d2 at 0: a query on a training point gets r off by
 // sqrt(1e-7) ~ 3e-4 and the variance off by twice that.
-template <int NU, bool ANISO, bool SYMMETRIC, bool DIRECT = SYMMETRIC>
+//
+// PROLOGUE (train form only): the launch also initialises the side buffers
+// of the factorization that follows it for its batch row — the first block
+// of every tile row copies its 32-entry segment of the caller's y row into
+// Z[b, :], and block (0, 0, b) sets logdet[b] = 0 and info[b] = 0. The
+// kernel boundary before panel 0 orders this; K's arithmetic is untouched.
+struct NmllPrologue {
+  const float* y;  // (N,) shared or (B, N) rows
+  int y_stride;    // 0 or N
+  float* Z;        // (B, N)
+  float* logdet;   // (B,)
+  int* info;       // (B,)
+};
+
+template <int NU, bool ANISO, bool SYMMETRIC, bool DIRECT = SYMMETRIC,
+          bool PROLOGUE = false>
 __global__ void matern_assemble_kernel(
     const float* __restrict__ Xq,   // (P, D) query rows (== X when SYMMETRIC)
     const float* __restrict__ X,    // (N, D)
@@ -51,8 +66,8 @@ __global__ void matern_assemble_kernel(
     float* __restrict__ K,          // (B, P, N)
     int P, int N, int D, int theta_stride, float jitter,
     const float* __restrict__ q_lb = nullptr,   // optional per-dim affine
-    const float* __restrict__ q_invrg = nullptr  // applied to Xq at load
-    ) {
+    const float* __restrict__ q_invrg = nullptr,  // applied to Xq at load
+    NmllPrologue pro = NmllPrologue()) {
   extern __shared__ float lds[];  // [2][TILE][DS] scaled row slabs
   const int DS = D | 1;  // odd stride: row base spreads over all 32 banks
   float* q_tile = lds;
@@ -63,6 +78,16 @@ __global__ void matern_assemble_kernel(
   const int tile_n = blockIdx.x * TILE;
   const float sf2 = __expf(theta[b * theta_stride + 0]);
   const float noise = __expf(theta[b * theta_stride + theta_stride - 1]);
+
+  if (PROLOGUE && blockIdx.x == 0) {
+    const int i = tile_p + (int)threadIdx.x;
+    if (threadIdx.x < TILE && i < N)
+      pro.Z[(long long)b * N + i] = pro.y[(long long)b * pro.y_stride + i];
+    if (blockIdx.y == 0 && threadIdx.x == TILE) {
+      pro.logdet[b] = 0.f;
+      pro.info[b] = 0;
+    }
+  }
 
   // stage scaled rows: thread t covers elements strided over TILE*D
   for (int idx = threadIdx.x; idx < TILE * D; idx += TPB) {
@@ -164,12 +189,12 @@ extern "C" void launch_matern_assemble_affine(
   #define DISPATCH(NU, AN, SY)                                              \
     hipLaunchKernelGGL((matern_assemble_kernel<NU, AN, SY>), grid, block,   \
                        lds_bytes, stream, Xq, X, theta, K, P, N, D,         \
-                       theta_stride, jitter, q_lb, q_invrg)
+                       theta_stride, jitter, q_lb, q_invrg, NmllPrologue())
   // symmetric: 0 = cross (norms+MFMA), 1 = train, 2 = cross, direct form
   #define DISPATCH_DIRECT(NU, AN)                                           \
     hipLaunchKernelGGL((matern_assemble_kernel<NU, AN, false, true>), grid, \
                        block, lds_bytes, stream, Xq, X, theta, K, P, N, D,  \
-                       theta_stride, jitter, q_lb, q_invrg)
+                       theta_stride, jitter, q_lb, q_invrg, NmllPrologue())
   #define DISPATCH_AN(NU)                                                   \
     if (symmetric == 2) {                                                   \
       if (aniso) DISPATCH_DIRECT(NU, true); else DISPATCH_DIRECT(NU, false); \
@@ -186,6 +211,33 @@ extern "C" void launch_matern_assemble_affine(
   }
   #undef DISPATCH_AN
   #undef DISPATCH_DIRECT
+  #undef DISPATCH
+}
+
+// Train-form assembly (launch_matern_assemble_affine with symmetric = 1) whose
+// launch also runs the NMLL prologue: Z = y rows, logdet = 0, info = 0.
+extern "C" void launch_matern_train_prologue(
+    const float* X, const float* theta, float* K, int B, int N, int D,
+    int theta_stride, float jitter, int nu_code, int aniso, const float* y,
+    int y_stride, float* Z, float* logdet, int* info, hipStream_t stream) {
+  dim3 grid((N + TILE - 1) / TILE, (N + TILE - 1) / TILE, B);
+  dim3 block(TPB);
+  size_t lds_bytes = (2 * TILE * (D | 1) + 2 * TILE) * sizeof(float);
+  const NmllPrologue pro = {y, y_stride, Z, logdet, info};
+  #define DISPATCH(NU, AN)                                                   \
+    hipLaunchKernelGGL((matern_assemble_kernel<NU, AN, true, true, true>),   \
+                       grid, block, lds_bytes, stream, X, X, theta, K, N, N, \
+                       D, theta_stride, jitter, (const float*)nullptr,       \
+                       (const float*)nullptr, pro)
+  #define DISPATCH_AN(NU) \
+    if (aniso) DISPATCH(NU, true); else DISPATCH(NU, false)
+  switch (nu_code) {
+    case 0: DISPATCH_AN(0); break;
+    case 1: DISPATCH_AN(1); break;
+    case 3: DISPATCH_AN(3); break;
+    default: DISPATCH_AN(5); break;
+  }
+  #undef DISPATCH_AN
   #undef DISPATCH
 }
 
