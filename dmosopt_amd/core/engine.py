@@ -139,6 +139,24 @@ def optimize_loop(
         import itertools
 
         it = itertools.count(1)
+    eligible = getattr(optimizer, "native_generations_eligible", None)
+    if eligible is not None and eligible(
+        mdl, termination, evaluator, optimize_mean_variance
+    ):
+        # native chunk driver: up to a prefetch chunk of generations per call,
+        # no Python between them; same results as the loop below
+        i = 1
+        while i <= num_generations:
+            counts, x_blk, y_blk = optimizer.run_generations_native(
+                num_generations - i + 1, mdl
+            )
+            x_new.append(x_blk)
+            y_new.append(y_blk)
+            for c in counts:
+                gen_indexes.append(np.full((c,), i, dtype=np.uint32))
+                n_eval += c
+                i += 1
+        it = ()
     for i in it:
         if termination is not None:
             pop_x, pop_y = optimizer.population_objectives

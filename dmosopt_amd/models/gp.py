@@ -424,6 +424,25 @@ class _GPRBase:
         mean, _ = self._fitted.predict(xq, return_var=self.return_mean_variance)
         return mean
 
+    def native_mean_args(self, device):
+        """The arguments evaluate_tensor gives the native posterior-mean call
+        after the queries — (X, theta, alpha, y_mean, y_std, nu, anisotropic,
+        q_lb, q_invrg) — for a caller that queues the same launches itself
+        (the NSGA-II chunk driver); None where evaluate_tensor would not take
+        the float32 native mean path on ``device``."""
+        device = torch.device(device)
+        if (
+            self.return_mean_variance
+            or self.compute == "bf16"
+            or self.dtype != torch.float32
+            or device.type != "cuda"
+            or torch.device(self.device) != device
+            or not ops.native_fp32(self._fitted.X)
+        ):
+            return None
+        cache, pa = self._native_pred_cache(device)
+        return tuple(pa) + (cache[1], cache[2])
+
     def gradient_tensor(self, x: torch.Tensor) -> torch.Tensor:
         """Device-resident gradient of the posterior mean in the query point:
         raw x (P, d) -> (P, m, d), [p, b, k] = d mean_b(x_p) / d x_k in raw

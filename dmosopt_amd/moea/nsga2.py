@@ -51,6 +51,12 @@ class NSGA2Optimizer(MOEA):
             p.mutation_rate = 1.0 / float(nInput)
         p.poolsize = int(round(p.popsize / 2.0))
         self.diversity_indicator = PopulationDiversity()
+        # the native generation path: -1 what DMOSOPT_GEN_FUSED says, 0 the
+        # chains of launches, 1 the fused spawn / select kernels; and whether
+        # whole chunks of generations may go to the native driver (same
+        # results on every route: tests/test_nsga2_gen_fused.py)
+        self.gen_fused = -1
+        self.native_chunks = True
 
     @property
     def default_parameters(self) -> Dict[str, Any]:
@@ -150,7 +156,7 @@ class NSGA2Optimizer(MOEA):
             res = spawn_generation_native(
                 population, rank, poolsize, 0.5, rng, popsize,
                 p.crossover_prob, p.mutation_prob, p.mutation_rate,
-                di_c, di_m, xlb_f, xub_f, prefetch=pf,
+                di_c, di_m, xlb_f, xub_f, prefetch=pf, fused=self.gen_fused,
             )
             if res is not None:
                 x_gen, crossover_indices, mutation_indices = res
@@ -206,13 +212,14 @@ class NSGA2Optimizer(MOEA):
                     x_gen.float().contiguous(), y_gen.float().contiguous(),
                     self.state.population_parm.float().contiguous(),
                     self.state.population_obj.float().contiguous(), popsize,
-                    c_idx_acc.contiguous(), sc, sm,
+                    c_idx_acc.contiguous(), sc, sm, fused=self.gen_fused,
                 )
             else:
                 parm, obj, rank, perm = _hipops.nsga2_select(
                     x_gen.float().contiguous(), y_gen.float().contiguous(),
                     self.state.population_parm.float().contiguous(),
                     self.state.population_obj.float().contiguous(), popsize,
+                    fused=self.gen_fused,
                 )
         else:
             population_parm = torch.cat([x_gen, self.state.population_parm], dim=0)
@@ -264,6 +271,104 @@ class NSGA2Optimizer(MOEA):
             self.update_population_size()
         if p.adaptive_operator_rates:
             self.update_operator_rates()
+
+    # ------------------------------------------------- native chunk driver
+    def native_generations_eligible(
+        self, mdl, termination=None, evaluator=None, optimize_mean_variance=False
+    ) -> bool:
+        """Whether engine.optimize_loop may hand whole chunks of generations
+        to run_generations_native: a float32 GPU population on the native
+        ops, the surrogate the fp32 native GP itself (no sharding, bf16 or
+        feasibility model), mean-only objectives, crowding, nothing that
+        looks at or changes the loop between two generations (termination,
+        evaluator, adaptive sizes or rates), shapes inside the fused kernels'
+        gate. False on CPU."""
+        st, p = self.state, self.opt_params
+        if st is None or termination is not None or evaluator is not None:
+            return False
+        if optimize_mean_variance or self.optimize_mean_variance:
+            return False
+        if not self.native_chunks or self.gen_fused == 0:
+            return False
+        x = st.population_parm
+        if (
+            not isinstance(x, torch.Tensor)
+            or x.device.type != "cuda"
+            or not ops.native_fp32(x, st.population_obj)
+            or st.rank.dtype != torch.long
+            or st.successful_crossovers.device != x.device
+        ):
+            return False
+        if self.x_distance_fns is not None or self.y_distance_metrics != ["crowding"]:
+            return False
+        if p.adaptive_population_size or p.adaptive_operator_rates:
+            return False
+        objective = getattr(mdl, "objective", None)
+        args_fn = getattr(objective, "native_mean_args", None)
+        if args_fn is None or getattr(mdl, "feasibility", None) is not None:
+            return False
+        from dmosopt_amd import _hipops
+
+        if self.gen_fused < 0 and not _hipops.gen_fused_default():
+            return False
+        pred = args_fn(x.device)
+        if pred is None:
+            return False
+        X, theta = pred[0], pred[1]
+        return (
+            x.shape[0] == p.popsize
+            and 1 <= p.poolsize <= p.popsize
+            and X.shape[1] == x.shape[1]
+            and theta.shape[0] == st.population_obj.shape[1]
+            # a generation's event stream ends at popsize - 1 .. popsize + 1 children
+            and _hipops.nsga2_generations_fit(
+                p.popsize, p.popsize + 1, st.population_obj.shape[1]
+            )
+        )
+
+    def run_generations_native(self, n_gen: int, mdl):
+        """Up to ``n_gen`` generations, at most what is left of one prefetch
+        chunk, queued by ONE native call (spawn, predict, select each): the
+        state, the counters and the draws from ``local_random`` are those of
+        as many generate / evaluate / update rounds. Returns (children per
+        generation, x_gen rows of all of them, their y_gen rows). Only where
+        native_generations_eligible."""
+        from dmosopt_amd import _hipops
+        from dmosopt_amd.moea.variation import _SpawnPrefetch
+
+        p, st = self.opt_params, self.state
+        population = st.population_parm
+        di_c, di_m = self._di_tensors(population)
+        bc = getattr(self, "_bounds_cache", None)
+        if bc is None or bc[0] != population.device:
+            xlb, xub = st.bounds[:, 0], st.bounds[:, 1]
+            bc = self._bounds_cache = (
+                population.device,
+                xlb.to(population.device, torch.float32).contiguous(),
+                xub.to(population.device, torch.float32).contiguous(),
+            )
+        pf = getattr(self, "_spawn_prefetch", None)
+        if pf is None:
+            pf = self._spawn_prefetch = _SpawnPrefetch()
+        items = pf.next_chunk(
+            self.local_random, p.popsize, p.poolsize, p.crossover_prob,
+            p.mutation_prob, population.device, n_gen,
+        )
+        meta, counts = [], []
+        for seed_t, C, M, seed_sbx, seed_mut, _, off in items:
+            meta += [seed_t, C, M, seed_sbx, seed_mut, *off[1:]]
+            counts.append(2 * C + M)
+            st.total_crossovers += C
+            st.total_mutations += M
+        x_all, y_all, parm, obj, rank = _hipops.nsga2_run_generations(
+            population.contiguous(), st.population_obj.contiguous(),
+            st.rank.contiguous(), p.poolsize, 0.5, items[0][6][0], meta,
+            di_c.float().contiguous(), di_m.float().contiguous(), bc[1], bc[2],
+            float(p.mutation_rate), *mdl.objective.native_mean_args(population.device),
+            st.successful_crossovers, st.successful_mutations,
+        )
+        st.population_parm, st.population_obj, st.rank = parm, obj, rank
+        return counts, x_all, y_all
 
     def get_population_strategy(self):
         return (

@@ -133,6 +133,7 @@ class _SpawnPrefetch:
     def __init__(self):
         self.key = None
         self.items = []
+        self.offs = []  # per item: (index buffer, offsets of its five lists)
 
     def refill(self, rng, popsize, poolsize, pc, pm, device):
         """Batched assembly: each numpy Generator call costs ~6 us of host
@@ -197,10 +198,12 @@ class _SpawnPrefetch:
         o_mi = o_ci + 2 * nC
         coff = np.concatenate([[0], np.cumsum(Cs)])
         moff = np.concatenate([[0], np.cumsum(Ms)])
-        items = []
+        items, offs = [], []
         for g in range(G):
             C0, C1 = int(coff[g]), int(coff[g + 1])
             M0, M1 = int(moff[g]), int(moff[g + 1])
+            # for the native chunk driver: the lists as offsets into dev
+            offs.append((dev, C0, o_i2 + C0, o_im + M0, o_ci + 2 * C0, o_mi + M0))
             items.append((
                 int(seeds[g, 0]), C1 - C0, M1 - M0, int(seeds[g, 1]),
                 int(seeds[g, 2]),
@@ -210,14 +213,30 @@ class _SpawnPrefetch:
                  dev[o_mi + M0 : o_mi + M1]),
             ))
         items.reverse()  # pop() yields generation order
+        offs.reverse()
         self.items = items
+        self.offs = offs
 
     def next(self, rng, popsize, poolsize, pc, pm, device):
         key = (popsize, poolsize, pc, pm, str(device))
         if key != self.key or not self.items:
             self.key = key
             self.refill(rng, popsize, poolsize, pc, pm, device)
+        self.offs.pop()
         return self.items.pop()
+
+    def next_chunk(self, rng, popsize, poolsize, pc, pm, device, n):
+        """Up to ``n`` consecutive generations of ONE refill (they share its
+        index buffer), refilling exactly where ``next`` would: the draws and
+        their order are those of ``n`` calls of ``next``."""
+        key = (popsize, poolsize, pc, pm, str(device))
+        if key != self.key or not self.items:
+            self.key = key
+            self.refill(rng, popsize, poolsize, pc, pm, device)
+        return [
+            self.items.pop() + (self.offs.pop(),)
+            for _ in range(min(n, len(self.items)))
+        ]
 
 
 def spawn_generation_native(
@@ -235,12 +254,15 @@ def spawn_generation_native(
     xlb: torch.Tensor,
     xub: torch.Tensor,
     prefetch: "_SpawnPrefetch" = None,
+    fused: int = -1,
 ):
     """Tournament selection + whole-generation variation in ONE extension
     call (generation_spawn binding): the host-dispatch-bound loop pays one
     binding round trip instead of two, and the pool tensor stays in C++.
     Returns (x_gen, crossover_slot_idx, mutation_slot_idx) or None when the
-    tournament kernel refuses the shape (caller uses the split path)."""
+    tournament kernel refuses the shape (caller uses the split path).
+    ``fused``: 1 the one-launch spawn kernel, 0 the tournament and variation
+    launches, -1 what DMOSOPT_GEN_FUSED says (same children either way)."""
     from dmosopt_amd import _hipops
 
     if prefetch is not None:
@@ -268,6 +290,7 @@ def spawn_generation_native(
         xlb.float().contiguous(), xub.float().contiguous(),
         float(mutation_rate), seed_sbx, seed_mut,
         rank_sorted=True,  # NSGA2 state.rank comes out of nsga2_select sorted
+        fused=int(fused),
     )
     if x_gen is None:
         return None

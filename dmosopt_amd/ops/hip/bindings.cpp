@@ -902,25 +902,85 @@ torch::Tensor crowding_distance(torch::Tensor Y) {
   return out;
 }
 
+// DMOSOPT_GEN_FUSED=0: the generation loop as before the fused select and
+// spawn kernels and the native chunk driver. The bindings take `fused` = -1
+// (this switch), 0 (the chains) or 1 (the fused kernels where they apply).
+static int GEN_FUSED = []() {
+  const char* e = getenv("DMOSOPT_GEN_FUSED");
+  return e && e[0] == '0' ? 0 : 1;
+}();
+
+bool gen_fused_default() { return GEN_FUSED != 0; }
+
+static bool gen_fused(int64_t fused) {
+  return fused < 0 ? GEN_FUSED != 0 : fused != 0;
+}
+
 // Fused NSGA2 survivor selection: concatenate children+parents, pareto-rank,
 // crowding, packed-key stable sort ((rank << 32) | ~float_bits(crowding)),
 // truncate to pop and gather — one python call instead of ~15 dispatched
 // ops per generation. Mirrors ops.remove_worst with the crowding metric.
-std::vector<torch::Tensor> nsga2_select(torch::Tensor x_gen,
-                                        torch::Tensor y_gen,
-                                        torch::Tensor pop_parm,
-                                        torch::Tensor pop_obj, int64_t pop) {
+// Where nsga2_select_fused_fits, all of it is TWO launches (grid-wide
+// dominator bits, then nsga2_select_fused_kernel; bitwise the chain's
+// outputs), the survivor accounting of nsga2_select_acc included; the chain
+// of launches below stays for larger N and with the switch off.
+static std::vector<torch::Tensor> nsga2_select_impl(
+    const torch::Tensor& x_gen, const torch::Tensor& y_gen,
+    const torch::Tensor& pop_parm, const torch::Tensor& pop_obj, int64_t pop,
+    const torch::Tensor* c_idx, const torch::Tensor* succ_cross,
+    const torch::Tensor* succ_mut, int64_t fused) {
   CHECK_GPU(x_gen);
+  CHECK_GPU(y_gen);
+  CHECK_GPU(pop_parm);
+  CHECK_GPU(pop_obj);
   TORCH_CHECK(x_gen.dtype() == torch::kFloat32 &&
-                  pop_parm.dtype() == torch::kFloat32,
+                  pop_parm.dtype() == torch::kFloat32 &&
+                  y_gen.dtype() == torch::kFloat32 &&
+                  pop_obj.dtype() == torch::kFloat32,
               "nsga2_select: float32 inputs required");
-  TORCH_CHECK(x_gen.size(1) == pop_parm.size(1) &&
+  TORCH_CHECK(x_gen.dim() == 2 && y_gen.dim() == 2 && pop_parm.dim() == 2 &&
+                  pop_obj.dim() == 2 && x_gen.size(1) == pop_parm.size(1) &&
                   y_gen.size(1) == pop_obj.size(1) &&
                   x_gen.size(0) == y_gen.size(0) &&
-                  pop_parm.size(0) == pop_obj.size(0),
+                  pop_parm.size(0) == pop_obj.size(0) && pop >= 1,
               "nsga2_select: shape mismatch");
+  if (c_idx) {
+    CHECK_GPU((*c_idx));
+    TORCH_CHECK(c_idx->dtype() == torch::kLong &&
+                    succ_cross->dtype() == torch::kLong &&
+                    succ_mut->dtype() == torch::kLong && succ_cross->is_cuda() &&
+                    succ_mut->is_cuda(),
+                "nsga2_select_acc: int64 GPU tensors required");
+  }
   const long long ng = x_gen.size(0), np_ = pop_parm.size(0);
   const long long dP = x_gen.size(1), dO = y_gen.size(1);
+  if (gen_fused(fused) && ng + np_ <= 2048 && dP >= 1 &&
+      nsga2_select_fused_fits((int)ng, (int)np_, (int)dO)) {
+    const int64_t P = std::min<int64_t>(pop, ng + np_);
+    auto lopt = x_gen.options().dtype(torch::kLong);
+    auto parm_o = torch::empty({P, dP}, x_gen.options());
+    auto obj_o = torch::empty({P, dO}, y_gen.options());
+    auto rank_o = torch::empty({P}, lopt);
+    auto perm = torch::empty({P}, lopt);
+    const int64_t Nf = ng + np_;
+    auto dbits = torch::empty({Nf * ((Nf + 31) / 32)},
+                              x_gen.options().dtype(torch::kInt32));
+    const int rc = launch_nsga2_select_fused(
+        x_gen.data_ptr<float>(), y_gen.data_ptr<float>(),
+        pop_parm.data_ptr<float>(), pop_obj.data_ptr<float>(), (int)ng,
+        (int)np_, (int)dP, (int)dO, (int)P,
+        c_idx ? (const long long*)c_idx->data_ptr<int64_t>() : nullptr,
+        c_idx ? (int)c_idx->numel() : 0, (unsigned int*)dbits.data_ptr<int>(),
+        parm_o.data_ptr<float>(),
+        obj_o.data_ptr<float>(), (long long*)rank_o.data_ptr<int64_t>(),
+        (long long*)perm.data_ptr<int64_t>(),
+        c_idx ? (long long*)succ_cross->data_ptr<int64_t>() : nullptr,
+        c_idx ? (long long*)succ_mut->data_ptr<int64_t>() : nullptr,
+        cur_stream());
+    TORCH_CHECK(rc == 0, "nsga2_select: fused selection refused its gate");
+    gp_check_launch("nsga2_select", "fused selection");
+    return {parm_o, obj_o, rank_o, perm};
+  }
   auto parm = torch::empty({ng + np_, dP}, x_gen.options());
   auto obj = torch::empty({ng + np_, dO}, y_gen.options());
   launch_cat_rows(x_gen.data_ptr<float>(), pop_parm.data_ptr<float>(),
@@ -976,7 +1036,22 @@ std::vector<torch::Tensor> nsga2_select(torch::Tensor x_gen,
                  (long long*)rank.data_ptr<int64_t>(), (long long*)perm.data_ptr<int64_t>(),
                  parm_o.data_ptr<float>(), obj_o.data_ptr<float>(),
                  (long long*)rank_o.data_ptr<int64_t>(), P, d, m, cur_stream());
+  if (c_idx)
+    launch_survivor_count(
+        (long long*)perm.data_ptr<int64_t>(),
+        (long long*)c_idx->data_ptr<int64_t>(), perm.size(0), c_idx->size(0),
+        (int)x_gen.size(0), (long long*)succ_cross->data_ptr<int64_t>(),
+        (long long*)succ_mut->data_ptr<int64_t>(), cur_stream());
   return {parm_o, obj_o, rank_o, perm};
+}
+
+std::vector<torch::Tensor> nsga2_select(torch::Tensor x_gen,
+                                        torch::Tensor y_gen,
+                                        torch::Tensor pop_parm,
+                                        torch::Tensor pop_obj, int64_t pop,
+                                        int64_t fused) {
+  return nsga2_select_impl(x_gen, y_gen, pop_parm, pop_obj, pop, nullptr,
+                           nullptr, nullptr, fused);
 }
 
 // nsga2_select + device-side operator-success accounting in ONE python
@@ -985,15 +1060,17 @@ std::vector<torch::Tensor> nsga2_select(torch::Tensor x_gen,
 std::vector<torch::Tensor> nsga2_select_acc(
     torch::Tensor x_gen, torch::Tensor y_gen, torch::Tensor pop_parm,
     torch::Tensor pop_obj, int64_t pop, torch::Tensor c_idx,
-    torch::Tensor succ_cross, torch::Tensor succ_mut) {
-  auto r = nsga2_select(x_gen, y_gen, pop_parm, pop_obj, pop);
-  auto& perm = r[3];
-  launch_survivor_count(
-      (long long*)perm.data_ptr<int64_t>(),
-      (long long*)c_idx.data_ptr<int64_t>(), perm.size(0), c_idx.size(0),
-      (int)x_gen.size(0), (long long*)succ_cross.data_ptr<int64_t>(),
-      (long long*)succ_mut.data_ptr<int64_t>(), cur_stream());
-  return r;
+    torch::Tensor succ_cross, torch::Tensor succ_mut, int64_t fused) {
+  return nsga2_select_impl(x_gen, y_gen, pop_parm, pop_obj, pop, &c_idx,
+                           &succ_cross, &succ_mut, fused);
+}
+
+static int gen_tour_torch_min_n() {
+  static int v = []() {
+    const char* e = getenv("DMOSOPT_TOUR_TORCH_MIN_N");
+    return e ? atoi(e) : (1 << 30);
+  }();
+  return v;
 }
 
 // Tournament pool + event-decoded variation chained inside one binding
@@ -1004,22 +1081,48 @@ torch::Tensor generation_spawn(
     torch::Tensor p1, torch::Tensor p2, torch::Tensor im, torch::Tensor di_c,
     torch::Tensor di_m, torch::Tensor lo, torch::Tensor hi,
     double mutation_rate, int64_t seed_sbx, int64_t seed_mut,
-    bool rank_sorted) {
+    bool rank_sorted, int64_t fused) {
   CHECK_GPU(population);
   TORCH_CHECK(population.dtype() == torch::kFloat32 &&
                   rank.dtype() == torch::kLong &&
                   poolsize <= population.size(0),
               "generation_spawn: f32 population, int64 rank");
   const int N = population.size(0), d = population.size(1);
+  if (gen_fused(fused) && N <= gen_tour_torch_min_n()) {
+    // ONE launch (spawn_fused_kernel) under launch_tournament's shape gate
+    CHECK_GPU(rank);
+    const int C = p1.size(0), M = im.size(0);
+    TORCH_CHECK(ci.dtype() == torch::kLong && mi.dtype() == torch::kLong &&
+                    p1.dtype() == torch::kLong && p2.dtype() == torch::kLong &&
+                    im.dtype() == torch::kLong && p2.size(0) == C &&
+                    ci.size(0) == 2 * (int64_t)C && mi.size(0) == M &&
+                    rank.size(0) == N && di_c.numel() == d &&
+                    di_m.numel() == d && lo.numel() == d && hi.numel() == d,
+                "generation_spawn: int64 slot/parent indices, (d,) bounds");
+    auto out = torch::empty({(long)(2 * C + M), d}, population.options());
+    if (C + M == 0) return out;
+    const float l1p = logf(1.0f - (float)p_sel);
+    if (launch_spawn_fused(
+            population.data_ptr<float>(), (long long*)rank.data_ptr<int64_t>(),
+            N, d, (int)poolsize, l1p, (unsigned long long)seed_t,
+            C ? (long long*)ci.data_ptr<int64_t>() : nullptr,
+            M ? (long long*)mi.data_ptr<int64_t>() : nullptr,
+            C ? (long long*)p1.data_ptr<int64_t>() : nullptr,
+            C ? (long long*)p2.data_ptr<int64_t>() : nullptr,
+            M ? (long long*)im.data_ptr<int64_t>() : nullptr,
+            di_c.data_ptr<float>(), di_m.data_ptr<float>(),
+            lo.data_ptr<float>(), hi.data_ptr<float>(), out.data_ptr<float>(),
+            C, M, (float)mutation_rate, (unsigned long long)seed_sbx,
+            (unsigned long long)seed_mut, cur_stream()) != 0)
+      return torch::Tensor();  // caller falls back to the split path
+    gp_check_launch("generation_spawn", "fused spawn");
+    return out;
+  }
   auto pool = torch::empty({poolsize, d}, population.options());
   auto pool_idx =
       torch::empty({poolsize}, population.options().dtype(torch::kLong));
   const float log1mp = logf(1.0f - (float)p_sel);
-  static int tour_torch_min_n = []() {
-    const char* e = getenv("DMOSOPT_TOUR_TORCH_MIN_N");
-    return e ? atoi(e) : (1 << 30);
-  }();
-  if (N > tour_torch_min_n) {
+  if (N > gen_tour_torch_min_n()) {
     auto r = tournament_torch(population, rank, poolsize, log1mp, seed_t,
                               rank_sorted);
     return variation_events(r[0].contiguous(), ci, mi, p1, p2, im, di_c,
@@ -1034,6 +1137,160 @@ torch::Tensor generation_spawn(
     return torch::Tensor();  // caller falls back to the split path
   return variation_events(pool, ci, mi, p1, p2, im, di_c, di_m, lo, hi,
                           mutation_rate, seed_sbx, seed_mut);
+}
+
+// Whether nsga2_run_generations takes a population of popsize rows with up to
+// max_children children a generation at m objectives: the gates of the fused
+// spawn and select kernels.
+bool nsga2_generations_fit(int64_t popsize, int64_t max_children, int64_t m) {
+  if (popsize < 1 || popsize > 2048 || max_children < 1 ||
+      max_children > 2048 || m < 1 || m > 64)
+    return false;
+  return nsga2_select_fused_fits((int)max_children, (int)popsize, (int)m) != 0;
+}
+
+// Native chunk driver of the NSGA-II generation loop: queues `meta.size() / 10`
+// generations — fused spawn, cross kernel, mean gemv, dominator bits and fused
+// select each — with
+// raw launches from one call: no Python and no allocation between them.
+//   pop_parm (P,d), pop_obj (P,m), rank (P,) int64: the state, P = popsize
+//   idx: the chunk's int64 index buffer (parents and child slots of every
+//     generation, as _SpawnPrefetch uploads it)
+//   meta: per generation seed_t, C, M, seed_sbx, seed_mut and the offsets of
+//     its i1, i2, im, ci, mi lists in idx
+// Returns {x_all (sum of children, d), y_all (., m), parm, obj, rank}: every
+// generation's children and their predicted objectives in their own rows,
+// and the state after the last generation. All five are views of the ONE
+// workspace this call allocates (the population ping-pongs between two
+// blocks of it), so no later call writes them.
+std::vector<torch::Tensor> nsga2_run_generations(
+    torch::Tensor pop_parm, torch::Tensor pop_obj, torch::Tensor rank,
+    int64_t poolsize, double p_sel, torch::Tensor idx,
+    std::vector<int64_t> meta, torch::Tensor di_c, torch::Tensor di_m,
+    torch::Tensor lo, torch::Tensor hi, double mutation_rate, torch::Tensor X,
+    torch::Tensor theta, torch::Tensor alpha, torch::Tensor y_mean,
+    torch::Tensor y_std, double nu, bool aniso,
+    c10::optional<torch::Tensor> q_lb, c10::optional<torch::Tensor> q_invrg,
+    torch::Tensor succ_cross, torch::Tensor succ_mut) {
+  const char* fn = "nsga2_run_generations";
+  const GpArgs g = gp_check_args(fn, X, theta, nu, aniso, q_lb, q_invrg);
+  gp_check_f32(fn, "pop_parm", pop_parm);
+  gp_check_f32(fn, "pop_obj", pop_obj);
+  gp_check_f32(fn, "alpha", alpha);
+  gp_check_f32(fn, "y_mean", y_mean);
+  gp_check_f32(fn, "y_std", y_std);
+  gp_check_f32(fn, "di_c", di_c);
+  gp_check_f32(fn, "di_m", di_m);
+  gp_check_f32(fn, "lo", lo);
+  gp_check_f32(fn, "hi", hi);
+  CHECK_GPU(rank);
+  CHECK_GPU(idx);
+  CHECK_GPU(succ_cross);
+  CHECK_GPU(succ_mut);
+  TORCH_CHECK(pop_parm.dim() == 2 && pop_obj.dim() == 2 &&
+                  pop_obj.size(0) == pop_parm.size(0) &&
+                  rank.numel() == pop_parm.size(0),
+              fn, ": pop_parm (P,d), pop_obj (P,m), rank (P,) required");
+  const int64_t P = pop_parm.size(0), d = pop_parm.size(1),
+                m = pop_obj.size(1);
+  TORCH_CHECK(rank.dtype() == torch::kLong && idx.dtype() == torch::kLong &&
+                  succ_cross.dtype() == torch::kLong &&
+                  succ_mut.dtype() == torch::kLong,
+              fn, ": rank, idx and the success counters must be int64");
+  TORCH_CHECK(d == g.D && m == g.B, fn, ": the model has ", g.D,
+              " inputs and ", g.B, " outputs, the population ", d, " and ", m);
+  TORCH_CHECK(alpha.numel() == g.B * g.N && y_mean.numel() == g.B &&
+                  y_std.numel() == g.B,
+              fn, ": alpha/y_mean/y_std shape mismatch");
+  TORCH_CHECK(di_c.numel() == d && di_m.numel() == d && lo.numel() == d &&
+                  hi.numel() == d,
+              fn, ": di_c, di_m, lo, hi must be (d,)");
+  TORCH_CHECK(poolsize >= 1 && poolsize <= P, fn, ": 1 <= poolsize <= P");
+  TORCH_CHECK(meta.size() % 10 == 0 && !meta.empty(), fn,
+              ": meta holds 10 values a generation");
+  const int64_t G = (int64_t)meta.size() / 10, n_idx = idx.numel();
+  int64_t total = 0, max_ng = 0;
+  for (int64_t k = 0; k < G; ++k) {
+    const int64_t* q = &meta[10 * k];
+    const int64_t C = q[1], M = q[2], ng = 2 * C + M;
+    TORCH_CHECK(C >= 0 && M >= 0 && ng >= 1, fn, ": generation ", k,
+                " has no children");
+    TORCH_CHECK(q[5] >= 0 && q[5] + C <= n_idx && q[6] >= 0 &&
+                    q[6] + C <= n_idx && q[7] >= 0 && q[7] + M <= n_idx &&
+                    q[8] >= 0 && q[8] + 2 * C <= n_idx && q[9] >= 0 &&
+                    q[9] + M <= n_idx,
+                fn, ": index lists of generation ", k, " leave idx");
+    total += ng;
+    max_ng = std::max(max_ng, ng);
+  }
+  TORCH_CHECK(nsga2_generations_fit(P, max_ng, m), fn,
+              ": shape outside the gate of the fused kernels");
+  gp_check_assemble(g, max_ng);
+
+  // one workspace: [rank A | rank B | perm] int64, then float32
+  // [x_all | y_all | parm A | parm B | obj A | obj B | Ks | dominator bits]
+  const int64_t n_long = 3 * P;
+  const int64_t n_bits = (P + max_ng) * ((P + max_ng + 31) / 32);
+  const int64_t n_f =
+      total * (d + m) + 2 * P * (d + m) + g.B * max_ng * g.N + n_bits;
+  auto ws = torch::empty({n_long * 8 + n_f * 4},
+                         pop_parm.options().dtype(torch::kUInt8));
+  auto wl = ws.slice(0, 0, n_long * 8).view(torch::kLong);
+  auto wf = ws.slice(0, n_long * 8, n_long * 8 + n_f * 4).view(torch::kFloat32);
+  int64_t o = 0;
+  auto take = [&](int64_t n) { auto t = wf.slice(0, o, o + n); o += n; return t; };
+  auto x_all = take(total * d).view({total, d});
+  auto y_all = take(total * m).view({total, m});
+  torch::Tensor parm_b[2] = {take(P * d).view({P, d}), take(P * d).view({P, d})};
+  torch::Tensor obj_b[2] = {take(P * m).view({P, m}), take(P * m).view({P, m})};
+  auto Ks = take(g.B * max_ng * g.N);
+  unsigned int* dbits = (unsigned int*)take(n_bits).data_ptr<float>();
+  torch::Tensor rank_b[2] = {wl.slice(0, 0, P), wl.slice(0, P, 2 * P)};
+  long long* perm = (long long*)wl.data_ptr<int64_t>() + 2 * P;
+
+  const long long* ix = (const long long*)idx.data_ptr<int64_t>();
+  const float log1mp = logf(1.0f - (float)p_sel);
+  hipStream_t stream = cur_stream();
+  const float* cp = pop_parm.data_ptr<float>();
+  const float* co = pop_obj.data_ptr<float>();
+  const long long* cr = (const long long*)rank.data_ptr<int64_t>();
+  int64_t row = 0;
+  for (int64_t k = 0; k < G; ++k) {
+    const int64_t* q = &meta[10 * k];
+    const int C = (int)q[1], M = (int)q[2], ng = 2 * C + M;
+    float* xg = x_all.data_ptr<float>() + row * d;
+    float* yg = y_all.data_ptr<float>() + row * m;
+    const int rc = launch_spawn_fused(
+        cp, cr, (int)P, (int)d, (int)poolsize, log1mp,
+        (unsigned long long)q[0], ix + q[8], ix + q[9], ix + q[5], ix + q[6],
+        ix + q[7], di_c.data_ptr<float>(), di_m.data_ptr<float>(),
+        lo.data_ptr<float>(), hi.data_ptr<float>(), xg, C, M,
+        (float)mutation_rate, (unsigned long long)q[3],
+        (unsigned long long)q[4], stream);
+    TORCH_CHECK(rc == 0, fn, ": fused spawn refused its gate");
+    launch_matern_assemble_affine(
+        xg, g.X.data_ptr<float>(), g.theta.data_ptr<float>(),
+        Ks.data_ptr<float>(), g.B, ng, g.N, g.D, g.p, 0.0f, g.nu,
+        g.aniso ? 1 : 0, 0, g.q_lb, g.q_invrg, stream);
+    launch_gp_mean_gemv(Ks.data_ptr<float>(), alpha.data_ptr<float>(),
+                        y_mean.data_ptr<float>(), y_std.data_ptr<float>(), yg,
+                        g.B, ng, g.N, g.B, stream);
+    const int w = (int)(k & 1);
+    const int rs = launch_nsga2_select_fused(
+        xg, yg, cp, co, ng, (int)P, (int)d, (int)m, (int)P, ix + q[8], 2 * C,
+        dbits, parm_b[w].data_ptr<float>(), obj_b[w].data_ptr<float>(),
+        (long long*)rank_b[w].data_ptr<int64_t>(), perm,
+        (long long*)succ_cross.data_ptr<int64_t>(),
+        (long long*)succ_mut.data_ptr<int64_t>(), stream);
+    TORCH_CHECK(rs == 0, fn, ": fused selection refused its gate");
+    cp = parm_b[w].data_ptr<float>();
+    co = obj_b[w].data_ptr<float>();
+    cr = (const long long*)rank_b[w].data_ptr<int64_t>();
+    row += ng;
+  }
+  gp_check_launch(fn, "generation chunk");
+  const int w = (int)((G - 1) & 1);
+  return {x_all, y_all, parm_b[w], obj_b[w], rank_b[w]};
 }
 
 std::vector<torch::Tensor> sbx_batch(torch::Tensor pool, torch::Tensor p1,
@@ -1318,9 +1575,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sceua_partition_pack", &sceua_partition_pack);
   m.def("gp_nmll_into", &gp_nmll_into,
         "gp_nmll into caller-owned K, Z, logdet, info, out (no allocation)");
-  m.def("nsga2_select", &nsga2_select, "Fused survivor selection (cat+rank+crowding+sort+gather)");
-  m.def("nsga2_select_acc", &nsga2_select_acc);
-  m.def("generation_spawn", &generation_spawn, py::arg("population"), py::arg("rank"), py::arg("poolsize"), py::arg("p_sel"), py::arg("seed_t"), py::arg("ci"), py::arg("mi"), py::arg("p1"), py::arg("p2"), py::arg("im"), py::arg("di_c"), py::arg("di_m"), py::arg("lo"), py::arg("hi"), py::arg("mutation_rate"), py::arg("seed_sbx"), py::arg("seed_mut"), py::arg("rank_sorted") = false);
+  m.def("nsga2_select", &nsga2_select, "Fused survivor selection (cat+rank+crowding+sort+gather)",
+        py::arg("x_gen"), py::arg("y_gen"), py::arg("pop_parm"), py::arg("pop_obj"), py::arg("pop"),
+        py::arg("fused") = -1);
+  m.def("nsga2_select_acc", &nsga2_select_acc, py::arg("x_gen"), py::arg("y_gen"),
+        py::arg("pop_parm"), py::arg("pop_obj"), py::arg("pop"), py::arg("c_idx"),
+        py::arg("succ_cross"), py::arg("succ_mut"), py::arg("fused") = -1);
+  m.def("gen_fused_default", &gen_fused_default,
+        "False under DMOSOPT_GEN_FUSED=0: the generation loop's chains of launches");
+  m.def("nsga2_generations_fit", &nsga2_generations_fit);
+  m.def("nsga2_run_generations", &nsga2_run_generations,
+        "Native chunk driver: spawn, predict and select of several generations in one call");
+  m.def("generation_spawn", &generation_spawn, py::arg("population"), py::arg("rank"), py::arg("poolsize"), py::arg("p_sel"), py::arg("seed_t"), py::arg("ci"), py::arg("mi"), py::arg("p1"), py::arg("p2"), py::arg("im"), py::arg("di_c"), py::arg("di_m"), py::arg("lo"), py::arg("hi"), py::arg("mutation_rate"), py::arg("seed_sbx"), py::arg("seed_mut"), py::arg("rank_sorted") = false, py::arg("fused") = -1);
   m.def("gp_predict_mean", &gp_predict_mean, "Fused cross-kernel + posterior mean",
         py::arg("Xq"), py::arg("X"), py::arg("theta"), py::arg("alpha"),
         py::arg("y_mean"), py::arg("y_std"), py::arg("nu"), py::arg("aniso"),

@@ -127,6 +127,22 @@ void launch_tournament_keys(float* gkey, int N, float log1mp, unsigned long long
 int launch_tournament(const float* population, const long long* rank, float* pool,
     long long* pool_idx, int N, int d, int poolsize, float log1mp, unsigned long long seed,
     hipStream_t stream);
+// tournament + event-decoded variation in one launch; -1, launching nothing, outside
+// launch_tournament's shape gate
+int launch_spawn_fused(const float* population, const long long* rank, int N, int d, int poolsize,
+    float log1mp, unsigned long long seed_t, const long long* ci, const long long* mi,
+    const long long* p1, const long long* p2, const long long* im, const float* di_c,
+    const float* di_m, const float* lo, const float* hi, float* out, int C, int M,
+    float mutation_rate, unsigned long long seed_sbx, unsigned long long seed_mut,
+    hipStream_t stream);
+// whole survivor selection in two launches (grid-wide dominator bits into dbits_scratch,
+// (ng + np) * ceil((ng + np) / 32) words; then one workgroup): 1 where its LDS block fits, and
+// the launches (-1, launching nothing, where it does not). succ_cross null skips the counts.
+int nsga2_select_fused_fits(int ng, int np, int m);
+int launch_nsga2_select_fused(const float* x_gen, const float* y_gen, const float* pop_parm,
+    const float* pop_obj, int ng, int np, int d, int m, int keep, const long long* c_idx,
+    int n_cross, unsigned int* dbits_scratch, float* parm_o, float* obj_o, long long* rank_o,
+    long long* perm, long long* succ_cross, long long* succ_mut, hipStream_t stream);
 int launch_survivor_count(const long long* perm, const long long* c_idx, int n_perm, int n_cross,
     int n_children, long long* succ_cross, long long* succ_mut, hipStream_t stream);
 void launch_pack_rank_crowd(const long long* rank, const float* crowd, long long* key, int N,

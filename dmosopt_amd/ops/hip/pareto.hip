@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "launchers.h"
+#include "moea_device.h"
 #include <math.h>
 
 #define PTILE 32
@@ -560,38 +561,12 @@ __global__ __launch_bounds__(TPB) void crowding_kernel(
   }
   __syncthreads();
 
-  // bitonic sort ascending (stable order not required: equal normalized
-  // values produce zero gaps either way)
-  for (int ksz = 2; ksz <= npow2; ksz <<= 1) {
-    for (int jsz = ksz >> 1; jsz > 0; jsz >>= 1) {
-      for (int i = threadIdx.x; i < npow2; i += TPB) {
-        const int ixj = i ^ jsz;
-        if (ixj > i) {
-          const bool up = ((i & ksz) == 0);
-          const bool swap = up ? (vals[i] > vals[ixj]) : (vals[i] < vals[ixj]);
-          if (swap) {
-            float tv = vals[i]; vals[i] = vals[ixj]; vals[ixj] = tv;
-            int tixx = idxs[i]; idxs[i] = idxs[ixj]; idxs[ixj] = tixx;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
-
-  // gaps: boundary = 1, interior = (vals[i+1] - vals[i-1]) / span.
-  // Each dim writes its own row of out (m, N) — NO atomics, so the sum
-  // order is fixed and results are bit-identical across replicated ranks
-  // (float atomicAdd order would not be).
-  const float l = vals[0];
-  const float h = vals[N - 1];
-  float s = h - l;
-  if (!(s > 0.f) || !isfinite(s)) s = 1.f;
-  for (int i = threadIdx.x; i < N; i += TPB) {
-    float d = (i == 0 || i == N - 1) ? 1.f : (vals[i + 1] - vals[i - 1]) / s;
-    if (isnan(d)) d = 0.f;
-    out[(long long)j * N + idxs[i]] = d;
-  }
+  // sort and gaps: the inline nsga2_select_fused_kernel runs too. Each dim
+  // writes its own row of out (m, N) — NO atomics, so the sum order is
+  // fixed and results are bit-identical across replicated ranks (float
+  // atomicAdd order would not be).
+  crowding_sort_gaps(vals, idxs, out + (long long)j * N, N, npow2,
+                     threadIdx.x, TPB);
 }
 
 // out must be an (m, N) buffer; the host sums over dim 0 deterministically.

@@ -7,28 +7,9 @@
 
 #include "common.h"
 #include "launchers.h"
+#include "moea_device.h"
 #include <math.h>
 
-
-// SBX / mutation child arithmetic with a PINNED fmaf order: under the
-// default -ffp-contract=fast the compiler may contract the blend
-// differently in different kernels (observed: sbx_batch_kernel vs
-// variation_events_kernel differed by ULPs for identical Philox draws),
-// which breaks the cross-path bitwise-identity guarantee the tests assert.
-__device__ __forceinline__ void sbx_children(float a, float b, float beta,
-                                             float lo, float hi, float* c1,
-                                             float* c2) {
-  const float x1 = 0.5f * fmaf(-beta, a, fmaf(beta, b, a + b));
-  const float x2 = 0.5f * fmaf(beta, a, fmaf(-beta, b, a + b));
-  *c1 = fminf(fmaxf(x1, lo), hi);
-  *c2 = fminf(fmaxf(x2, lo), hi);
-}
-
-__device__ __forceinline__ float mutated_child(float p, float delta, float lo,
-                                               float hi) {
-  const float v = fmaf(hi - lo, delta, p);
-  return fminf(fmaxf(v, lo), hi);
-}
 
 // children layout: C pairs first (child1 rows [0,C), child2 rows [C,2C))
 // — the host reorders into event order with an index gather.
@@ -166,32 +147,9 @@ __global__ void variation_events_kernel(
     unsigned long long seed_sbx, unsigned long long seed_mut) {
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (long long)(C + M) * d) return;
-  const int ev = (int)(idx / d);
-  const int g = (int)(idx % d);
-  if (ev < C) {
-    const float a = pool[p1[ev] * d + g];
-    const float b = pool[p2[ev] * d + g];
-    const Philox4 r = philox4x32(seed_sbx, (unsigned long long)ev * d + g);
-    const float u = u01(r.c0);
-    const float e = 1.f / (di_c[g] + 1.f);
-    const float beta = (u <= 0.5f) ? __powf(2.f * u, e)
-                                   : __powf(1.f / (2.f * (1.f - u)), e);
-    float c1, c2;
-    sbx_children(a, b, beta, lo[g], hi[g], &c1, &c2);
-    out[ci[2 * ev] * d + g] = c1;
-    out[ci[2 * ev + 1] * d + g] = c2;
-  } else {
-    const int m = ev - C;
-    const float p = pool[im[m] * d + g];
-    const Philox4 ph =
-        philox4x32(seed_mut ^ 0x5deece66dULL, (unsigned long long)m * d + g);
-    const float u = u01(ph.c0);
-    const float e = 1.f / (di_m[g] + 1.f);
-    const float delta = (u < mutation_rate)
-                            ? __powf(2.f * u, e) - 1.f
-                            : 1.f - __powf(2.f * (1.f - u), e);
-    out[mi[m] * d + g] = mutated_child(p, delta, lo[g], hi[g]);
-  }
+  variation_event_gene<long long>(pool, nullptr, ci, mi, p1, p2, im, di_c, di_m,
+                                  lo, hi, out, (int)(idx / d), (int)(idx % d),
+                                  C, d, mutation_rate, seed_sbx, seed_mut);
 }
 
 extern "C" void launch_variation_events(
