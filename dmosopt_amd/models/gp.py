@@ -43,6 +43,43 @@ def _top_k_mo(x: np.ndarray, y: np.ndarray, top_k):
     return xt.numpy() if xt is not x else x, yt.numpy() if yt is not y else y
 
 
+#: Thompson mode draws its path from a generator seeded with the model's
+#: ``seed`` plus this offset
+THOMPSON_SEED_OFFSET = 1
+
+
+class GPPath:
+    """Posterior sample paths of a GP model in the model's raw input units
+    (``model.sample_paths``): every call of ``evaluate`` / ``evaluate_tensor``
+    queries the SAME drawn functions. Values are (P, m), or (P, S, m) for
+    S = n_paths > 1. ``sample`` is the gp_core.GPPathSample behind it."""
+
+    def __init__(self, model, sample):
+        self._model = model
+        self.sample = sample
+
+    def evaluate(self, x) -> np.ndarray:
+        """Raw numpy x (P, d) or (d,) -> float64 path values."""
+        mdl = self._model
+        xin = np.asarray(x, dtype=np.float64)
+        if xin.ndim == 1:
+            xin = xin.reshape(1, mdl.nInput)
+        xn = (xin - mdl.xlb[None, :]) / mdl.xrg[None, :]
+        Xq = torch.as_tensor(xn, dtype=mdl.dtype, device=mdl.device)
+        return self.sample.evaluate_normalized(Xq).cpu().numpy().astype(np.float64)
+
+    def evaluate_tensor(self, x: torch.Tensor) -> torch.Tensor:
+        """Raw device tensor x (P, d) -> device tensor, no host trip; on the
+        native path the per-dimension normalization happens inside the
+        kernel loads."""
+        mdl = self._model
+        xr = x.to(mdl.device, mdl.dtype)
+        if ops.gp_mean_grad_native(xr, mdl._fitted.X):
+            cache, _ = mdl._native_pred_cache(xr.device)
+            return self.sample.evaluate_affine(xr.contiguous(), cache[1], cache[2])
+        return self.sample.evaluate_normalized(mdl.normalize_query(xr))
+
+
 class _GPRBase:
     nu: float = 2.5
     #: fitted state is fully determined by (archive, theta): the engine may
@@ -78,8 +115,23 @@ class _GPRBase:
         compute="fp32",
         logger=None,
         theta_override=None,
+        thompson=False,
+        path_features=1024,
         **kwargs,
     ):
+        if thompson and return_mean_variance:
+            raise ValueError(
+                "thompson=True optimizes one posterior sample path per "
+                "objective; it cannot be combined with return_mean_variance=True"
+            )
+        #: Thompson-sampling mode: evaluate / evaluate_tensor answer from ONE
+        #: posterior sample path drawn right after the fit (n_features =
+        #: path_features, seed = THOMPSON_SEED_OFFSET + the model's seed);
+        #: predict, gradient* and evaluate_mean_variance_tensor stay the
+        #: posterior's
+        self.thompson = bool(thompson)
+        self.path_features = int(path_features)
+        self._thompson_path: Optional[GPPath] = None
         self.nInput = nInput
         self.nOutput = nOutput
         self.xlb = np.asarray(xlb, dtype=np.float64)
@@ -147,6 +199,7 @@ class _GPRBase:
                 compute=self.compute,
             )
             self.theta = theta
+            self._draw_thompson_path(seed)
             return
 
         if optimizer == "dlib" and logger is not None:
@@ -209,6 +262,19 @@ class _GPRBase:
             compute=self.compute,
         )
         self.theta = theta
+        self._draw_thompson_path(seed)
+
+    def _draw_thompson_path(self, seed):
+        """Thompson mode: draw the path the inner optimizer will see. Its
+        seed is ``seed + THOMPSON_SEED_OFFSET`` (None stays None), so the draw
+        never shares a generator state with the hyperparameter search, which
+        seeds its own streams with ``seed`` itself; archive, theta and seed
+        are replicated, so every rank draws the same path."""
+        if self.thompson:
+            self._thompson_path = self.sample_paths(
+                1, self.path_features,
+                None if seed is None else int(seed) + THOMPSON_SEED_OFFSET,
+            )
 
     def _fit_adam(self, X, Yn, bl, bu, nopt, m, lr, iters, seed):
         g = torch.Generator(device="cpu")
@@ -354,7 +420,19 @@ class _GPRBase:
             self._nq_cache = cache = (key, lb, rg)
         return (xin - cache[1]) / cache[2]
 
+    def sample_paths(self, n_paths=1, n_features=1024, seed=None) -> GPPath:
+        """Draw ``n_paths`` functions from every objective's posterior
+        (FittedGP.sample_paths: ``n_features`` random Fourier features plus
+        the Matheron update, everything random from one generator seeded with
+        ``seed``). Returns a GPPath with ``evaluate(x)`` (raw numpy in,
+        float64 out) and ``evaluate_tensor(x)`` (raw device tensor in, device
+        tensor out). A ``compute="bf16"`` model answers from the float32
+        form."""
+        return GPPath(self, self._fitted.sample_paths(n_paths, n_features, seed))
+
     def evaluate(self, x):
+        if self._thompson_path is not None:
+            return self._thompson_path.evaluate(x)
         mean, var = self.predict(x)
         if self.return_mean_variance:
             return mean, var
@@ -409,7 +487,10 @@ class _GPRBase:
         )
 
     def evaluate_tensor(self, x: torch.Tensor) -> torch.Tensor:
-        """Device-resident evaluate: tensor in, tensor out, no host trip."""
+        """Device-resident evaluate: tensor in, tensor out, no host trip. In
+        Thompson mode the values are those of the model's sample path."""
+        if self._thompson_path is not None:
+            return self._thompson_path.evaluate_tensor(x)
         xr = x.to(self.device, self.dtype)
         if (
             not self.return_mean_variance
@@ -429,10 +510,12 @@ class _GPRBase:
         after the queries — (X, theta, alpha, y_mean, y_std, nu, anisotropic,
         q_lb, q_invrg) — for a caller that queues the same launches itself
         (the NSGA-II chunk driver); None where evaluate_tensor would not take
-        the float32 native mean path on ``device``."""
+        the float32 native mean path on ``device`` (Thompson mode included:
+        its evaluate_tensor is a sample path, not the mean)."""
         device = torch.device(device)
         if (
             self.return_mean_variance
+            or self._thompson_path is not None
             or self.compute == "bf16"
             or self.dtype != torch.float32
             or device.type != "cuda"

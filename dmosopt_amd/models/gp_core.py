@@ -530,6 +530,8 @@ class FittedGP:
             self.L, _, info = ops.chol_factor_batched_bf16(K)
         else:
             self.L, _, info = ops.chol_factor_batched(K)  # (m, N, N)
+        # noise + the jitter each objective's L was actually factored with
+        self.diag_add = torch.exp(theta[:, -1]) + jitter  # (m,)
         if int(info.sum()) != 0:
             # escalate jitter for failed objectives
             for _ in range(5):
@@ -542,6 +544,8 @@ class FittedGP:
                 )
                 L2, _, info = ops.chol_factor_batched(K2)
                 self.L = torch.where(bad[:, None, None], L2, self.L)
+                self.diag_add = torch.where(
+                    bad, torch.exp(theta[:, -1]) + jitter, self.diag_add)
         Yn = (Y - y_mean[None, :]) / y_std[None, :]  # (N, m) standardized
         yb = Yn.T[:, :, None].contiguous()  # (m, N, 1)
         self.alpha = ops.chol_solve_batched(self.L, yb)  # (m, N, 1)
@@ -634,6 +638,74 @@ class FittedGP:
                 self.nu, self.anisotropic,
             )
 
+    def sample_paths(self, n_paths: int = 1, n_features: int = 1024,
+                     seed: Optional[int] = None) -> "GPPathSample":
+        """Draw ``n_paths`` functions from the posterior of every objective
+        (decoupled pathwise sampling, Wilson et al. 2020; formulas in
+        docs/surrogates.md): a random-Fourier-feature prior draw with
+        ``n_features`` cosines plus the Matheron update through the training
+        data. Each draw is ONE consistent function that can be queried at
+        new points any number of times.
+
+        Batch row s * m + b is path s of objective b. Everything random comes
+        from one CPU ``torch.Generator`` seeded with ``seed`` (unseeded: the
+        generator's fixed default), in float64 and in this order, each block
+        shaped (S, m, ...):
+
+        1. ``randn(S, m, M, D)``   z, the spectral directions
+        2. ``randn(S, m, M, 2 nu)`` n, whose mean square is g (Matern only;
+           nothing is drawn for the RBF kernel, where g = 1)
+        3. ``rand(S, m, M)``        tau, the phase offsets in turns
+        4. ``randn(S, m, M)``       w, the feature weights
+        5. ``randn(S, m, N)``       e, with eps = sqrt(diag_add) * e
+
+        so CPU fits, GPU fits and every rank of one seed hold the same draws
+        (a float32 fit differs from a float64 one only through its theta).
+        Omega = z / (ell sqrt(g)) / (2 pi), tau and amp = sqrt(2 sf2 / M) w
+        are stored rounded to float32, and the path is DEFINED by the stored
+        values. A ``compute="bf16"`` fit answers from the float32 form: fp32
+        cross kernel, and ``self.L`` as it is."""
+        S, M = int(n_paths), int(n_features)
+        if S < 1 or M < 1:
+            raise ValueError("n_paths and n_features must be >= 1")
+        m, (N, D) = self.theta.shape[0], self.X.shape
+        g = torch.Generator(device="cpu")
+        if seed is not None:
+            g.manual_seed(int(seed))
+        f64 = torch.float64
+        theta = self.theta.detach().to("cpu", f64)
+        z = torch.randn(S, m, M, D, generator=g, dtype=f64)
+        if self.nu is None or self.nu == float("inf"):
+            root_g = torch.ones(S, m, M, 1, dtype=f64)
+        else:
+            n = torch.randn(S, m, M, int(round(2 * self.nu)), generator=g, dtype=f64)
+            root_g = torch.sqrt((n * n).mean(dim=-1, keepdim=True))
+        tau = torch.rand(S, m, M, generator=g, dtype=f64)
+        w = torch.randn(S, m, M, generator=g, dtype=f64)
+        e = torch.randn(S, m, N, generator=g, dtype=f64)
+        ell = torch.exp(theta[:, 1 : 1 + D] if self.anisotropic else theta[:, 1:2])
+        Omega = z / (ell[None, :, None, :] * root_g) / (2.0 * math.pi)
+        amp = torch.sqrt(2.0 * torch.exp(theta[:, 0]) / M)[None, :, None] * w
+        dev, dt = self.X.device, self.X.dtype
+        eps = (torch.sqrt(self.diag_add.detach().to("cpu", f64))[None, :, None] * e
+               ).reshape(S * m, N).to(device=dev, dtype=dt)
+        sample = GPPathSample(
+            self, S,
+            Omega.reshape(S * m, M, D).to(device=dev, dtype=torch.float32),
+            tau.reshape(S * m, M).to(device=dev, dtype=torch.float32),
+            amp.reshape(S * m, M).to(device=dev, dtype=torch.float32),
+            eps,
+        )
+        with _single_threaded_cpu_math(not self.X.is_cuda):
+            # f(X) through the routine the queries use, with no update term
+            fX = sample._values(self.X, None, None, standardized=True).T  # (B, N)
+            corr = ops.chol_solve_batched(
+                self.L.repeat(S, 1, 1), (fX.to(dt) + eps)[:, :, None].contiguous()
+            )
+            # K^-1 (y_n - f(X) - eps), with K^-1 y_n the fit's alpha
+            sample.alpha = (self.alpha[:, :, 0].repeat(S, 1) - corr[:, :, 0]).contiguous()
+        return sample
+
     def _finish_var(self, Xq, Ks, mean_n):
         sf2 = torch.exp(self.theta[:, 0])
         noise = torch.exp(self.theta[:, -1])
@@ -647,3 +719,67 @@ class FittedGP:
         var_n = (kss - quad).clamp_min(0.0)  # (m, P)
         var = (self.y_std[None, :] ** 2) * var_n.T
         return self._destandardize(mean_n), var
+
+
+class GPPathSample:
+    """``n_paths`` posterior sample paths of every objective of a FittedGP
+    (FittedGP.sample_paths). Batch row s * m + b is path s of objective b:
+
+        path(x) = y_mean_b + y_std_b (f(u) + k_b(u, X) alpha_row),
+        f(u)    = sum_j amp_j cos(2 pi (tau_j + Omega_j . u)).
+
+    Omega (B, M, D), tau (B, M) and amp (B, M) are float32 and define the
+    path; eps (B, N) is the noise draw of the Matheron update and alpha
+    (B, N) its weights K^-1 (y_n - f(X) - eps), both in the fit's dtype. At
+    the training inputs path_n(X) = y_n - eps - diag_add * alpha holds
+    whatever the number of features.
+    """
+
+    def __init__(self, fit: FittedGP, n_paths: int, Omega, tau, amp, eps):
+        self.fit = fit
+        self.n_paths = n_paths
+        self.Omega, self.tau, self.amp, self.eps = Omega, tau, amp, eps
+        S = n_paths
+        self.theta = fit.theta.repeat(S, 1)
+        self.y_mean = fit.y_mean.repeat(S)
+        self.y_std = fit.y_std.repeat(S)
+        self.alpha = torch.zeros_like(eps)
+        self._pred: Optional[tuple] = None
+
+    def _values(self, Xq, q_lb, q_invrg, standardized=False):
+        """(P, B) path values at Xq (raw with q_lb / q_invrg, unit box
+        without); ``standardized`` leaves y_mean / y_std out."""
+        f = self.fit
+        if standardized:
+            y_mean, y_std = torch.zeros_like(self.y_mean), torch.ones_like(self.y_std)
+        else:
+            y_mean, y_std = self.y_mean, self.y_std
+        if not standardized and ops.gp_mean_grad_native(Xq, f.X):
+            if self._pred is None or self._pred[0] is not self.alpha:
+                # per-draw arguments of the native call, converted once
+                self._pred = (self.alpha, ops.gp_pred_args(
+                    f.X, self.theta, self.alpha, y_mean, y_std, f.nu, f.anisotropic))
+            return ops.gp_predict_path_cached(
+                Xq.float().contiguous(), self._pred[1], self.Omega, self.tau,
+                self.amp, q_lb, q_invrg,
+            )
+        return ops.gp_predict_path(
+            Xq, f.X, self.theta, self.alpha, y_mean, y_std, f.nu, f.anisotropic,
+            self.Omega, self.tau, self.amp, q_lb, q_invrg,
+        )
+
+    def _shape(self, vals: torch.Tensor) -> torch.Tensor:
+        m = self.fit.theta.shape[0]
+        return vals if self.n_paths == 1 else vals.reshape(-1, self.n_paths, m)
+
+    def evaluate_normalized(self, Xq: torch.Tensor) -> torch.Tensor:
+        """Path values at unit-box queries Xq (P, d) -> (P, S, m) in the units
+        of Y, (P, m) when S = 1."""
+        with _single_threaded_cpu_math(not Xq.is_cuda):
+            return self._shape(self._values(Xq, None, None))
+
+    def evaluate_affine(self, Xq, q_lb, q_invrg) -> torch.Tensor:
+        """evaluate_normalized at u = (Xq - q_lb) * q_invrg for raw queries;
+        on the native path the affine is applied inside the kernel loads."""
+        with _single_threaded_cpu_math(not Xq.is_cuda):
+            return self._shape(self._values(Xq, q_lb, q_invrg))

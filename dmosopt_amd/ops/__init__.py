@@ -321,6 +321,64 @@ def gp_predict_mean_grad(
     )
 
 
+def gp_predict_path_cached(Xq, pred_args, Omega, tau, amp, q_lb, q_invrg):
+    """Native sample-path values (P, B) of float32 queries (raw with q_lb /
+    q_invrg) after the caller has passed gp_mean_grad_native itself.
+    ``pred_args`` is gp_pred_args output with the path's weights alpha' in the
+    alpha slot; Omega, tau, amp are contiguous float32."""
+    return _native.gp_predict_path(Xq, *pred_args, Omega, tau, amp, q_lb, q_invrg)
+
+
+def gp_predict_path(
+    Xq, X, theta, alpha_path, y_mean, y_std, nu, anisotropic, Omega, tau, amp,
+    q_lb=None, q_invrg=None,
+):
+    """Values of one GP posterior sample path per batch row, (P, B):
+
+        y_mean_b + y_std_b (k_b(u, X) alpha_path_b
+                            + sum_j amp_bj cos(2 pi (tau_bj + Omega_bj . u)))
+
+    with u the queries (raw with q_lb / q_invrg, unit box without). Float32
+    GPU tensors with D <= 128 run the posterior-mean launches with alpha_path
+    and the feature kernels of ops/hip/gp_path.hip in one extension call;
+    everything else the cross kernel, a bmm and
+    torch_ref.gp_path_features_ref, in the dtype of X."""
+    if gp_mean_grad_native(Xq, X):
+        return gp_predict_path_cached(
+            Xq.float().contiguous(),
+            gp_pred_args(X, theta, alpha_path, y_mean, y_std, nu, anisotropic),
+            Omega.float().contiguous(), tau.float().contiguous(),
+            amp.float().contiguous(),
+            None if q_lb is None else q_lb.float().contiguous(),
+            None if q_invrg is None else q_invrg.float().contiguous(),
+        )
+    return gp_predict_path_composed(
+        Xq, X, theta, alpha_path, y_mean, y_std, nu, anisotropic, Omega, tau, amp,
+        q_lb, q_invrg,
+    )
+
+
+def gp_predict_path_composed(
+    Xq, X, theta, alpha_path, y_mean, y_std, nu, anisotropic, Omega, tau, amp,
+    q_lb=None, q_invrg=None,
+):
+    """gp_predict_path as a composition of torch ops in the dtype of X, on
+    any device: the dispatched cross kernel, a bmm and the reference
+    features."""
+    from dmosopt_amd.models import gp_core
+
+    dt = X.dtype
+    B = theta.shape[0]
+    u = Xq.to(dt)
+    if q_lb is not None:
+        u = (u - q_lb.to(dt)) * q_invrg.to(dt)
+    Ks = gp_core.build_kernel(u, X, theta.to(dt), nu=nu, anisotropic=anisotropic)
+    upd = torch.bmm(Ks, alpha_path.to(dt).reshape(B, -1, 1))[:, :, 0]  # (B, P)
+    feat = torch_ref.gp_path_features_ref(u, Omega, tau, amp)
+    return (y_mean.to(dt).reshape(B)[None, :]
+            + y_std.to(dt).reshape(B)[None, :] * (upd + feat).T)
+
+
 def sceua_propose(cx, lcs, bl, bu, nps, seed):
     return _native.sceua_propose(cx, lcs, bl, bu, nps, seed)
 

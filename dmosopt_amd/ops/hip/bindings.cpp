@@ -388,6 +388,57 @@ std::vector<torch::Tensor> gp_predict_mean_grad(
   return {f.out, jac};
 }
 
+// One posterior sample path per batch row at the queries, (P, B):
+//   y_mean_b + y_std_b * (k_b(u, X) alpha_path_b + sum_j amp_bj
+//                         cos(2 pi (tau_bj + Omega_bj . u))).
+// The Matheron-update term is gp_predict_mean's front end with alpha_path
+// (the same launches, so amp = 0 gives gp_predict_mean's bits); the
+// random-feature kernels (gp_path.hip) then add their term into that block.
+// Omega (B,M,D) in turns per unit of the normalised query, tau (B,M) in
+// turns, amp (B,M). The (B, S, P) scratch is bounded by slicing P: a
+// query's value does not depend on its slice.
+torch::Tensor gp_predict_path(
+    torch::Tensor Xq, torch::Tensor X, torch::Tensor theta,
+    torch::Tensor alpha_path, torch::Tensor y_mean, torch::Tensor y_std,
+    double nu, bool aniso, torch::Tensor Omega, torch::Tensor tau,
+    torch::Tensor amp, c10::optional<torch::Tensor> q_lb = c10::nullopt,
+    c10::optional<torch::Tensor> q_invrg = c10::nullopt) {
+  const GpArgs g =
+      gp_check_args("gp_predict_path", X, theta, nu, aniso, q_lb, q_invrg);
+  gp_check_f32(g.fn, "Omega", Omega);
+  gp_check_f32(g.fn, "tau", tau);
+  gp_check_f32(g.fn, "amp", amp);
+  TORCH_CHECK(Omega.dim() == 3 && Omega.size(0) == g.B && Omega.size(2) == g.D,
+              g.fn, ": Omega must be (B,M,D)");
+  const int64_t M = Omega.size(1);
+  TORCH_CHECK(tau.numel() == g.B * M && amp.numel() == g.B * M, g.fn,
+              ": tau and amp must be (B,M)");
+  // the feature kernel stages a 32-query and a 64-feature slab of D|1 floats
+  // in the default 64 KiB of LDS; grid.y carries the feature chunks
+  TORCH_CHECK(g.D <= 128 && g.B <= 65535 && M >= 1 && M <= 4194240, g.fn,
+              ": shape exceeds the launch bounds of the feature stage "
+              "(D <= 128, B <= 65535, 1 <= M <= 4194240)");
+  const int64_t S = gp_path_splits((int)M);
+  auto f = gp_predict_front(g, Xq, alpha_path, y_mean, y_std, g.B);
+  const int64_t P = Xq.size(0);
+  // at most 64 MiB of partials per slice, whole 32-query tiles
+  const int64_t per_query = g.B * S * (int64_t)sizeof(float);
+  const int64_t slice =
+      std::min(P, std::max<int64_t>(32, ((64LL << 20) / per_query) / 32 * 32));
+  auto part = torch::empty({g.B, S, slice}, X.options());
+  for (int64_t p0 = 0; p0 < P; p0 += slice) {
+    const int64_t Pc = std::min(slice, P - p0);
+    const int rc = launch_gp_path(
+        Xq.data_ptr<float>() + p0 * g.D, Omega.data_ptr<float>(),
+        tau.data_ptr<float>(), amp.data_ptr<float>(), y_std.data_ptr<float>(),
+        part.data_ptr<float>(), f.out.data_ptr<float>() + p0 * g.B, (int)g.B,
+        (int)Pc, (int)M, (int)g.D, (int)g.B, g.q_lb, g.q_invrg, cur_stream());
+    TORCH_CHECK(rc == 0, g.fn, ": feature kernel launch failed: ",
+                hipGetErrorString((hipError_t)rc));
+  }
+  return f.out;
+}
+
 // Fused mean + variance predict (optimize_mean_variance mode): the front end
 // of gp_predict_mean writes the left half of the (P, 2B) block, and the
 // |Linv k*|^2 variance kernels (gp_variance.hip) read the same cross kernel
@@ -1601,6 +1652,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Fused posterior mean (P, B) and its query-point gradient (P, B, D)",
         py::arg("Xq"), py::arg("X"), py::arg("theta"), py::arg("alpha"),
         py::arg("y_mean"), py::arg("y_std"), py::arg("nu"), py::arg("aniso"),
+        py::arg("q_lb") = py::none(), py::arg("q_invrg") = py::none());
+  m.def("gp_predict_path", &gp_predict_path,
+        "Posterior sample path (P, B): mean launches with alpha_path + random features",
+        py::arg("Xq"), py::arg("X"), py::arg("theta"), py::arg("alpha_path"),
+        py::arg("y_mean"), py::arg("y_std"), py::arg("nu"), py::arg("aniso"),
+        py::arg("Omega"), py::arg("tau"), py::arg("amp"),
         py::arg("q_lb") = py::none(), py::arg("q_invrg") = py::none());
   m.def("gp_nmll", &gp_nmll, "Fused batched GP NMLL (assemble+chol+solve+reduce)");
   m.def("gp_nmll_grad", &gp_nmll_grad,

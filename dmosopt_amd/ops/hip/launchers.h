@@ -69,6 +69,13 @@ int launch_gp_mean_grad(const float* Xq, const float* X, const float* theta, con
     const float* y_std, float* part, float* jac, int B, int P, int N, int D, int p, int nu_code,
     int aniso, const float* q_lb, const float* q_invrg, hipStream_t stream);
 
+// --------------------------------------------------------------- gp_path.hip
+int gp_path_splits(int M);
+// adds y_std_b * sum_j amp_bj cos(2 pi (tau_bj + Omega_bj . u)) into out[p * ldo + b]
+int launch_gp_path(const float* Xq, const float* Omega, const float* tau, const float* amp,
+    const float* y_std, float* part, float* out, int B, int P, int M, int D, int ldo,
+    const float* q_lb, const float* q_invrg, hipStream_t stream);
+
 // ----------------------------------------------------------- sceua_stage.hip
 void launch_sceua_propose(const float* cx, const int* lcs, const float* bl, const float* bu,
     float* cand, int S, int G, int npg, int nopt, int nps, unsigned long long seed,

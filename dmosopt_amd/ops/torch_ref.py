@@ -500,3 +500,37 @@ def gp_predict_mean_grad_ref(Xq: Tensor, X: Tensor, theta: Tensor, alpha: Tensor
     for k in range(D):
         jac[:, :, k] = ((w * s_k(k)).sum(dim=2) * scale[:, k : k + 1]).T
     return mean, jac
+
+
+def gp_path_features_ref(U: Tensor, Omega: Tensor, tau: Tensor, amp: Tensor) -> Tensor:
+    """Random-Fourier-feature term of a GP sample path in plain torch, on any
+    device: U (P, D) unit-box queries, Omega (B, M, D) frequencies in turns
+    per unit, tau (B, M) offsets in turns, amp (B, M) -> (B, P),
+
+        f[b, p] = sum_j amp_bj cos(2 pi (tau_bj + sum_d Omega_bjd U_pd)).
+
+    The phase is always formed in float64 from the given values (tau first,
+    then one dimension at a time in index order, as the kernel of
+    ops/hip/gp_path.hip does) and reduced to the turn fraction t - round(t)
+    there: heavy-tailed frequencies give phases of 1e3..1e5 turns. The cosine
+    and the sum over the features run in the dtype of U. Batch rows are
+    walked in slices that bound the (B, P, M) temporaries.
+    """
+    import math
+
+    dt = U.dtype
+    B, M, D = Omega.shape
+    P = U.shape[0]
+    U64, amp_t = U.double(), amp.to(dt)
+    out = torch.empty(B, P, dtype=dt, device=U.device)
+    step = max(1, (1 << 22) // max(1, P * M))
+    for b0 in range(0, B, step):
+        Om = Omega[b0 : b0 + step].double()
+        t = tau[b0 : b0 + step].double()[:, None, :].expand(-1, P, -1).clone()
+        for k in range(D):
+            t += Om[:, None, :, k] * U64[None, :, k, None]
+        frac = (t - torch.round(t)).to(dt)
+        out[b0 : b0 + step] = (
+            amp_t[b0 : b0 + step, None, :] * torch.cos((2.0 * math.pi) * frac)
+        ).sum(dim=2)
+    return out

@@ -36,6 +36,7 @@ ext = CUDAExtension(
         os.path.join("dmosopt_amd", "ops", "hip", "gp_variance.hip"),
         os.path.join("dmosopt_amd", "ops", "hip", "gp_nmll_grad.hip"),
         os.path.join("dmosopt_amd", "ops", "hip", "gp_mean_grad.hip"),
+        os.path.join("dmosopt_amd", "ops", "hip", "gp_path.hip"),
     ],
     include_dirs=[HIP_DIR],
     extra_compile_args={
