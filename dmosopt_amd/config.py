@@ -67,6 +67,7 @@ sensitivity_registry = {
 
 feasibility_registry = {
     "logreg": "dmosopt_amd.models.feasibility.LogisticFeasibilityModel",
+    "gp": "dmosopt_amd.models.feasibility.GPFeasibilityModel",
 }
 
 

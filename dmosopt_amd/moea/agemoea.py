@@ -19,7 +19,7 @@ import torch
 from dmosopt_amd import ops
 from dmosopt_amd.datatypes import Struct
 from dmosopt_amd.hv.indicators import PopulationDiversity
-from dmosopt_amd.moea.base import MOEA
+from dmosopt_amd.moea.base import MOEA, device_rank
 from dmosopt_amd.moea.variation import event_stream_variation
 
 
@@ -194,6 +194,21 @@ def environmental_selection(
         rank = ops.pareto_rank(torch.as_tensor(ys)).cpu().numpy()
     order = np.argsort(rank, kind="stable")
     xs, ys, rank = xs[order], ys[order], rank[order]
+
+    def feas_rank(front):
+        """The model's rank of the rows ``front`` of the sorted population:
+        evaluated on the device where the model has a rank_tensor and the
+        population is a GPU tensor (only the front's (n,) result comes to the
+        host, where the greedy survival bookkeeping runs), through numpy
+        otherwise."""
+        if isinstance(population_parm, torch.Tensor):
+            rows = torch.as_tensor(order[front], device=population_parm.device)
+            on_device = device_rank(
+                getattr(feasibility_model, "rank_tensor", None), population_parm[rows])
+            if on_device is not None:
+                return on_device.double().cpu().numpy()
+        return feasibility_model.rank(xs[front])
+
     rmax = int(rank.max())
 
     yn = np.zeros_like(ys)
@@ -220,7 +235,7 @@ def environmental_selection(
             else:
                 sort_keys = []
                 if feasibility_model is not None:
-                    sort_keys.append(-feasibility_model.rank(xs[front_r]))
+                    sort_keys.append(-feas_rank(front_r))
                 sort_keys.append(-crowd_dist[front_r])
                 perm = np.lexsort(tuple(sort_keys))
                 selected[front_r[perm[: pop - count]]] = True
@@ -228,7 +243,7 @@ def environmental_selection(
     else:
         sort_keys = []
         if feasibility_model is not None:
-            sort_keys.append(-feasibility_model.rank(xs[front_1]))
+            sort_keys.append(-feas_rank(front_1))
         sort_keys.append(-crowd_dist[front_1])
         perm = np.lexsort(tuple(sort_keys))
         selected[front_1[perm[:pop]]] = True

@@ -19,6 +19,17 @@ from dmosopt_amd import sampling
 from dmosopt_amd.datatypes import Struct
 
 
+def device_rank(rank_tensor, x):
+    """The feasibility rank of the population ``x`` evaluated on the device:
+    ``rank_tensor(x)`` where the model has that method (``rank_tensor`` is
+    what the optimizer looked up on ``model.feasibility`` once) and x is a
+    GPU tensor; None otherwise, and the caller takes the host route (numpy
+    in, numpy out)."""
+    if rank_tensor is None or not (isinstance(x, torch.Tensor) and x.is_cuda):
+        return None
+    return rank_tensor(x)
+
+
 class MOEA:
     def __init__(self, name: str, popsize: int, nInput: int, nOutput: int, **kwargs):
         self.name = name

@@ -25,14 +25,22 @@ import torch
 from dmosopt_amd import ops
 from dmosopt_amd.datatypes import Struct
 from dmosopt_amd.hv.indicators import HypervolumeImprovement, PopulationDiversity
-from dmosopt_amd.moea.base import MOEA
+from dmosopt_amd.moea.base import MOEA, device_rank
 
 
-def _sort_mo(x: torch.Tensor, y: torch.Tensor, x_distance_fns=None):
-    """(perm, rank) by pareto rank then per-front x-distance (CMAES.py:458)."""
+def _sort_mo(x: torch.Tensor, y: torch.Tensor, x_distance_fns=None,
+             x_rank_tensor=None):
+    """(perm, rank) by pareto rank then per-front x-distance (CMAES.py:458).
+    ``x_rank_tensor``: the feasibility model's device form of the one
+    x-distance function, or None."""
     rank = ops.pareto_rank(y)
     keys = [rank.to(torch.float64)]
-    if x_distance_fns:
+    on_device = device_rank(x_rank_tensor, x) if x_distance_fns else None
+    if on_device is not None:
+        # the rank is a per-row function of x: one call over the whole
+        # population gives every front's values, with no host trip
+        keys = [-on_device.to(torch.float64)] + keys
+    elif x_distance_fns:
         rank_np = rank.cpu().numpy()
         xd = np.zeros(len(rank_np))
         xnp = x.cpu().numpy()
@@ -112,8 +120,11 @@ class CMAESOptimizer(MOEA):
         super().__init__(name="CMAES", popsize=popsize, nInput=nInput, nOutput=nOutput, **kwargs)
         self.model = model
         self.x_distance_fns = None
+        self.x_rank_tensor = None
         if model is not None and getattr(model, "feasibility", None) is not None:
             self.x_distance_fns = [model.feasibility.rank]
+            # the same rank on the device, where the model offers it
+            self.x_rank_tensor = getattr(model.feasibility, "rank_tensor", None)
         p = self.opt_params
         if np.isscalar(p.di_mutation):
             p.di_mutation = np.full(nInput, float(p.di_mutation))
@@ -153,7 +164,7 @@ class CMAESOptimizer(MOEA):
         Ainv = eye[None].repeat(P, 1, 1)
         pc = torch.zeros(P, dim, dtype=self.dtype, device=self.device)
         psucc = torch.full((P,), p.ptarg, dtype=self.dtype, device=self.device)
-        perm, rank = _sort_mo(x, y, self.x_distance_fns)
+        perm, rank = _sort_mo(x, y, self.x_distance_fns, self.x_rank_tensor)
         sel = perm[:P]
         return Struct(
             bounds=bounds,
@@ -178,7 +189,8 @@ class CMAESOptimizer(MOEA):
         arz = torch.as_tensor(
             rng.normal(size=(lambda_ * mu, dim)), dtype=self.dtype, device=self.device
         )
-        perm, rank = _sort_mo(st.parents_x, st.parents_y, self.x_distance_fns)
+        perm, rank = _sort_mo(st.parents_x, st.parents_y, self.x_distance_fns,
+                              self.x_rank_tensor)
         rank_np = rank.cpu().numpy()
         parent_selection = []
         count = 0
@@ -207,7 +219,8 @@ class CMAESOptimizer(MOEA):
         if n <= popsize:
             chosen = np.ones(n, dtype=bool)
             return chosen, np.zeros(n, dtype=bool), ops.pareto_rank(candidates_y).cpu().numpy()
-        perm, rank = _sort_mo(candidates_x, candidates_y, self.x_distance_fns)
+        perm, rank = _sort_mo(candidates_x, candidates_y, self.x_distance_fns,
+                              self.x_rank_tensor)
         rank_np = rank.cpu().numpy()
         order_inv = np.argsort(perm.cpu().numpy(), kind="stable")
         chosen = np.zeros(n, dtype=bool)

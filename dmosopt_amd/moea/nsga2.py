@@ -18,7 +18,7 @@ import torch
 
 from dmosopt_amd import ops
 from dmosopt_amd.datatypes import Struct
-from dmosopt_amd.moea.base import MOEA
+from dmosopt_amd.moea.base import MOEA, device_rank
 from dmosopt_amd.hv.indicators import PopulationDiversity
 
 
@@ -39,8 +39,11 @@ class NSGA2Optimizer(MOEA):
         self.optimize_mean_variance = optimize_mean_variance
         self.y_distance_metrics = [distance_metric] if distance_metric is not None else None
         self.x_distance_fns = None
+        self.x_rank_tensor = None
         if model is not None and getattr(model, "feasibility", None) is not None:
             self.x_distance_fns = [model.feasibility.rank]
+            # the same rank on the device, where the model offers it
+            self.x_rank_tensor = getattr(model.feasibility, "rank_tensor", None)
 
         p = self.opt_params
         if np.isscalar(p.di_crossover):
@@ -93,6 +96,9 @@ class NSGA2Optimizer(MOEA):
     def _x_dists(self, x: torch.Tensor):
         if self.x_distance_fns is None:
             return None
+        on_device = device_rank(self.x_rank_tensor, x)
+        if on_device is not None:  # no host trip
+            return [on_device]
         out = []
         for fn in self.x_distance_fns:
             v = fn(x.cpu().numpy()) if not isinstance(x, np.ndarray) else fn(x)

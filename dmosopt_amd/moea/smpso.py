@@ -18,7 +18,7 @@ import torch
 from dmosopt_amd import ops
 from dmosopt_amd.datatypes import Struct
 from dmosopt_amd.hv.indicators import PopulationDiversity
-from dmosopt_amd.moea.base import MOEA
+from dmosopt_amd.moea.base import MOEA, device_rank
 
 
 def velocity_vector(rng, position, velocity, archive, crowding, xlb, xub):
@@ -78,8 +78,11 @@ class SMPSOOptimizer(MOEA):
         self.distance_metric = distance_metric
         self.y_distance_metrics = [distance_metric] if distance_metric is not None else None
         self.x_distance_fns = None
+        self.x_rank_tensor = None
         if model is not None and getattr(model, "feasibility", None) is not None:
             self.x_distance_fns = [model.feasibility.rank]
+            # the same rank on the device, where the model offers it
+            self.x_rank_tensor = getattr(model.feasibility, "rank_tensor", None)
         p = self.opt_params
         if np.isscalar(p.di_mutation):
             p.di_mutation = np.full(nInput, float(p.di_mutation))
@@ -113,6 +116,9 @@ class SMPSOOptimizer(MOEA):
     def _x_dists(self, x):
         if self.x_distance_fns is None:
             return None
+        on_device = device_rank(self.x_rank_tensor, x)
+        if on_device is not None:  # no host trip
+            return [on_device]
         return [
             torch.as_tensor(np.asarray(fn(x.cpu().numpy())), dtype=x.dtype, device=x.device)
             for fn in self.x_distance_fns

@@ -21,7 +21,7 @@ from dmosopt_amd.hv.indicators import (
     PopulationDiversity,
     SlidingWindow,
 )
-from dmosopt_amd.moea.base import MOEA
+from dmosopt_amd.moea.base import MOEA, device_rank
 
 
 @dataclass
@@ -55,8 +55,11 @@ class TRSOptimizer(MOEA):
         super().__init__(name="TRS", popsize=popsize, nInput=nInput, nOutput=nOutput, **kwargs)
         self.model = model
         self.x_distance_fns = None
+        self.x_rank_tensor = None
         if model is not None and getattr(model, "feasibility", None) is not None:
             self.x_distance_fns = [model.feasibility.rank]
+            # the same rank on the device, where the model offers it
+            self.x_rank_tensor = getattr(model.feasibility, "rank_tensor", None)
         self.indicator = HypervolumeImprovement
         self.diversity_indicator = PopulationDiversity()
         self.optimize_mean_variance = optimize_mean_variance
@@ -74,6 +77,9 @@ class TRSOptimizer(MOEA):
     def _x_dists(self, x):
         if self.x_distance_fns is None:
             return None
+        on_device = device_rank(self.x_rank_tensor, x)
+        if on_device is not None:  # no host trip
+            return [on_device]
         return [
             torch.as_tensor(np.asarray(fn(x.cpu().numpy())), dtype=x.dtype, device=x.device)
             for fn in self.x_distance_fns

@@ -283,6 +283,37 @@ def gp_predict_mean_var_fused(
     return None
 
 
+def gp_predict_pof_cached(Xq, pred_args, Linv, q_lb, q_invrg):
+    """Native (P, B + 1) block [PoF | rank] of float32 queries (raw with
+    q_lb / q_invrg): PoF_b = Phi(z_b) with z_b the posterior mean over the
+    noise-inclusive posterior deviation (ops/hip/gp_pof.hip), rank the mean
+    over b in column order. Arguments as gp_predict_mean_var_cached, after
+    the caller has passed native_fp32 itself."""
+    return _native.gp_predict_pof(
+        Xq, *pred_args[:3], Linv, *pred_args[3:], q_lb, q_invrg
+    )
+
+
+def gp_predict_pof(
+    Xq, X, theta, alpha, Linv, y_mean, y_std, nu, anisotropic,
+    q_lb=None, q_invrg=None,
+):
+    """GP probability of feasibility, (P, B + 1) = [PoF | rank]. Float32 GPU
+    tensors run the fused native call; everything else (CPU, float64, forced
+    torch) torch_ref.gp_predict_pof_ref in the dtype of X."""
+    if Xq.is_cuda and native_fp32(X):
+        return gp_predict_pof_cached(
+            Xq.float().contiguous(),
+            gp_pred_args(X, theta, alpha, y_mean, y_std, nu, anisotropic),
+            Linv.contiguous().float(),
+            None if q_lb is None else q_lb.float().contiguous(),
+            None if q_invrg is None else q_invrg.float().contiguous(),
+        )
+    return torch_ref.gp_predict_pof_ref(
+        Xq, X, theta, alpha, Linv, y_mean, y_std, nu, anisotropic, q_lb, q_invrg
+    )
+
+
 #: widest input the gradient kernel takes (16 dimensions per thread)
 GP_MEAN_GRAD_MAX_D = 128
 

@@ -480,6 +480,39 @@ torch::Tensor gp_predict_mean_var(
   return f.out;
 }
 
+// Probability of feasibility of a GP regressed on constraint values: the
+// (P, B + 1) block [PoF_0 .. PoF_{B-1} | rank], PoF_b = Phi(z_b) with z_b the
+// posterior mean over the noise-inclusive posterior deviation, rank their
+// mean in column order. gp_predict_mean_var's launches up to the epilogue
+// (the means go to a (P, B) scratch block), then the finish of gp_pof.hip.
+torch::Tensor gp_predict_pof(
+    torch::Tensor Xq, torch::Tensor X, torch::Tensor theta,
+    torch::Tensor alpha, torch::Tensor Linv, torch::Tensor y_mean,
+    torch::Tensor y_std, double nu, bool aniso,
+    c10::optional<torch::Tensor> q_lb = c10::nullopt,
+    c10::optional<torch::Tensor> q_invrg = c10::nullopt) {
+  const GpArgs g =
+      gp_check_args("gp_predict_pof", X, theta, nu, aniso, q_lb, q_invrg);
+  gp_check_f32(g.fn, "Linv", Linv);
+  TORCH_CHECK(Linv.dim() == 3 && Linv.size(0) == g.B && Linv.size(1) == g.N &&
+                  Linv.size(2) == g.N,
+              g.fn, ": Linv must be (B,N,N)");
+  auto f = gp_predict_front(g, Xq, alpha, y_mean, y_std, g.B);
+  // nu = 1/2: the variance reads the direct-difference cross kernel, as in
+  // gp_predict_mean_var
+  torch::Tensor Kv = g.nu == 1 ? gp_assemble(g, Xq, 1, 2, 0.0f) : f.Ks;
+  const int64_t P = Xq.size(0);
+  auto part = torch::empty({g.B, (int64_t)gp_var_tiles((int)g.N), P}, X.options());
+  auto out = torch::empty({P, g.B + 1}, X.options());
+  const int rc = launch_gp_pof(
+      Linv.data_ptr<float>(), Kv.data_ptr<float>(), f.out.data_ptr<float>(),
+      theta.data_ptr<float>(), y_std.data_ptr<float>(), part.data_ptr<float>(),
+      out.data_ptr<float>(), g.B, P, g.N, g.p, cur_stream());
+  TORCH_CHECK(rc == 0, g.fn, ": feasibility kernel launch failed: ",
+              hipGetErrorString((hipError_t)rc));
+  return out;
+}
+
 // Fused SCE-UA CCE stage: candidate proposal and acceptance+resort, one
 // extension call each instead of ~30 torch kernels per stage.
 // Fused tournament selection: stable rank sort + Gumbel top-k weighted
@@ -1648,6 +1681,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("Linv"), py::arg("y_mean"), py::arg("y_std"), py::arg("nu"),
         py::arg("aniso"), py::arg("q_lb") = py::none(),
         py::arg("q_invrg") = py::none(), py::arg("var_decimals") = -1);
+  m.def("gp_predict_pof", &gp_predict_pof,
+        "Fused GP probability of feasibility, (P, B + 1) = [Phi(mean / sd) | row mean]",
+        py::arg("Xq"), py::arg("X"), py::arg("theta"), py::arg("alpha"),
+        py::arg("Linv"), py::arg("y_mean"), py::arg("y_std"), py::arg("nu"),
+        py::arg("aniso"), py::arg("q_lb") = py::none(),
+        py::arg("q_invrg") = py::none());
   m.def("gp_predict_mean_grad", &gp_predict_mean_grad,
         "Fused posterior mean (P, B) and its query-point gradient (P, B, D)",
         py::arg("Xq"), py::arg("X"), py::arg("theta"), py::arg("alpha"),

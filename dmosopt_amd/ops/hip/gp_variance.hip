@@ -153,6 +153,21 @@ __global__ void gp_var_finish_kernel(const float* __restrict__ part,
   out[(long long)p * (2 * B) + B + b] = v;
 }
 
+extern "C" int gp_var_tiles(int N) { return (N + GV_TILE - 1) / GV_TILE; }
+
+// The partial sums alone, part: (B, gp_var_tiles(N), P) floats of scratch;
+// the epilogue is the caller's (the variance finish below, or the
+// probability-of-feasibility finish of gp_pof.hip).
+extern "C" int launch_gp_var_partial(const float* Linv, const float* Ks,
+                                     float* part, int B, int P, int N,
+                                     hipStream_t stream) {
+  const int T = gp_var_tiles(N);
+  dim3 grid((P + GV_TILE - 1) / GV_TILE, T, B);
+  hipLaunchKernelGGL(gp_var_partial_kernel, grid, dim3(GV_TPB), 0, stream,
+                     Linv, Ks, part, P, N, T);
+  return (int)hipGetLastError();
+}
+
 // part: (B, ceil(N/32), P) floats of scratch; out: (P, 2B), columns [B, 2B)
 // are written here. Returns the hipGetLastError() code of the launches.
 extern "C" int launch_gp_variance(const float* Linv, const float* Ks,
@@ -160,12 +175,9 @@ extern "C" int launch_gp_variance(const float* Linv, const float* Ks,
                                   float* part, float* out, int B, int P,
                                   int N, int theta_stride, float round_scale,
                                   hipStream_t stream) {
-  const int T = (N + GV_TILE - 1) / GV_TILE;
-  dim3 grid((P + GV_TILE - 1) / GV_TILE, T, B);
-  hipLaunchKernelGGL(gp_var_partial_kernel, grid, dim3(GV_TPB), 0, stream,
-                     Linv, Ks, part, P, N, T);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return (int)err;
+  const int T = gp_var_tiles(N);
+  const int rc = launch_gp_var_partial(Linv, Ks, part, B, P, N, stream);
+  if (rc != 0) return rc;
   const long long n = (long long)B * P;
   hipLaunchKernelGGL(gp_var_finish_kernel, dim3((int)((n + 255) / 256)),
                      dim3(256), 0, stream, part, theta, y_std, out, B, P, T,

@@ -55,6 +55,16 @@ void launch_chol_syrk_bf16(float* A, int N, int k0, int n_pairs, int B, hipStrea
 int launch_gp_variance(const float* Linv, const float* Ks, const float* theta, const float* y_std,
     float* part, float* out, int B, int P, int N, int theta_stride, float round_scale,
     hipStream_t stream);
+// row tiles of Linv = partial sums per query; the partial sums alone into part (B, tiles, P)
+int gp_var_tiles(int N);
+int launch_gp_var_partial(const float* Linv, const float* Ks, float* part, int B, int P, int N,
+    hipStream_t stream);
+
+// ---------------------------------------------------------------- gp_pof.hip
+// mean: the (P, B) de-standardised means of launch_gp_mean_gemv; out (P, B + 1) = [PoF | rank]
+int launch_gp_pof(const float* Linv, const float* Ks, const float* mean, const float* theta,
+    const float* y_std, float* part, float* out, int B, int P, int N, int theta_stride,
+    hipStream_t stream);
 
 // ---------------------------------------------------------- gp_nmll_grad.hip
 int launch_gp_fill_identity(float* Y, int B, int N, hipStream_t stream);

@@ -534,3 +534,76 @@ def gp_path_features_ref(U: Tensor, Omega: Tensor, tau: Tensor, amp: Tensor) -> 
             amp_t[b0 : b0 + step, None, :] * torch.cos((2.0 * math.pi) * frac)
         ).sum(dim=2)
     return out
+
+
+def gp_predict_pof_ref(Xq: Tensor, X: Tensor, theta: Tensor, alpha: Tensor,
+                       Linv: Tensor, y_mean: Tensor, y_std: Tensor, nu,
+                       anisotropic: bool, q_lb: Optional[Tensor] = None,
+                       q_invrg: Optional[Tensor] = None,
+                       L: Optional[Tensor] = None) -> Tensor:
+    """GP probability of feasibility in plain torch, in the dtype of X, on
+    any device: the (P, B + 1) block [PoF_0 .. PoF_{B-1} | rank].
+
+    Xq (P, D) raw queries with q_lb / q_invrg, unit-box queries without;
+    alpha (B, N) or (B, N, 1); Linv (B, N, N) = L^-1 of the fit. With the
+    standardised posterior mean mu_n = k* alpha and the noise-inclusive
+    variance var_n = max(sf2 + noise - |Linv k*|^2, 0):
+
+        z_b   = (mu_n + y_mean_b / y_std_b) / sqrt(max(var_n, 1e-12))
+        PoF_b = 0.5 erfc(-z_b / sqrt 2)        (accurate in both tails)
+        rank  = (1/B) sum_b PoF_b              (added in column order)
+
+    The closed form of ops/hip/gp_pof.hip, which replaces it on float32 GPU
+    fits. With the factor ``L`` (B, N, N) given, Linv k* is the triangular
+    solve L v = k* that FittedGP.predict uses on the CPU and ``Linv`` is not
+    read (it may be None): the two agree to rounding, but the explicit
+    inverse carries cond(L) once more, ~1e-11 of PoF in float64.
+
+    nu = 1/2 only: the variance reads a direct-difference cross kernel, as
+    the native bindings do (its kernel has an infinite slope in d2 at 0, so
+    the cancellation of the norms-form d2 reaches the variance); the mean
+    keeps the norms form.
+    """
+    import math
+
+    from dmosopt_amd.models.gp_core import build_kernel_torch
+
+    dt = X.dtype
+    B = theta.shape[0]
+    theta, Xq = theta.to(dt), Xq.to(dt)
+    y_mean, y_std = y_mean.to(dt).reshape(B), y_std.to(dt).reshape(B)
+    u = Xq if q_lb is None else (Xq - q_lb.to(dt)) * q_invrg.to(dt)
+    Ks = build_kernel_torch(u, X, theta, nu=nu, anisotropic=anisotropic)  # (B,P,N)
+    mean_n = torch.bmm(Ks, alpha.to(dt).reshape(B, -1, 1))[:, :, 0]  # (B, P)
+    if nu == 0.5:
+        D = X.shape[1]
+        inv_ell = (torch.exp(-theta[:, 1 : 1 + D]) if anisotropic
+                   else torch.exp(-theta[:, 1:2])).expand(B, D)
+        d2 = torch.zeros_like(Ks)
+        for k in range(D):  # one dimension at a time: no (B, P, N, D) temporary
+            t = (u[None, :, None, k] - X[None, None, :, k]) * inv_ell[:, None, None, k]
+            d2 += t * t
+        Ks = torch.exp(theta[:, 0])[:, None, None] * torch.exp(-torch.sqrt(d2))
+    if L is not None:
+        v = torch.linalg.solve_triangular(L.to(dt), Ks.transpose(1, 2), upper=False)
+    else:
+        v = torch.bmm(Linv.to(dt), Ks.transpose(1, 2))  # (B, N, P)
+    kss = torch.exp(theta[:, 0]) + torch.exp(theta[:, -1])
+    var_n = (kss[:, None] - (v * v).sum(dim=1)).clamp_min(0.0)
+    z = (mean_n + (y_mean / y_std)[:, None]) / torch.sqrt(var_n.clamp_min(1e-12))
+    pof = 0.5 * torch.special.erfc(-z * math.sqrt(0.5))  # (B, P)
+    out = torch.empty(Xq.shape[0], B + 1, dtype=dt, device=X.device)
+    out[:, :B] = pof.T
+    out[:, B] = mean_in_column_order(out[:, :B])
+    return out
+
+
+def mean_in_column_order(P: Tensor) -> Tensor:
+    """Row means of P (n, C) with the columns added one at a time in index
+    order, then one division by C: the order the feasibility kernel uses, so
+    the result does not depend on how a reduction splits the row. The
+    divisor is a tensor: a scalar one may become a multiplication by 1/C."""
+    s = P[:, 0].clone()
+    for b in range(1, P.shape[1]):
+        s += P[:, b]
+    return s / torch.full_like(s, P.shape[1])
