@@ -552,24 +552,29 @@ def chol_factor_batched(K):
 
 
 CHOL_SCHEDULES = {"classic": 0, "lookahead": 1}
+# diagonal factor of the panel; None = the process default
+# (DMOSOPT_CHOL_FACTOR, "reg" unless set to "lds")
+CHOL_FACTORS = {None: -1, "lds": 0, "reg": 1}
 
 
-def chol_factor_multik(K, rhs=None, schedule="classic"):
+def chol_factor_multik(K, rhs=None, schedule="classic", factor=None):
     """Multi-launch factorization of K (B,N,N) with an EXPLICIT trailing-
-    update schedule ("classic" or "lookahead") and an optional rhs (B,N)
+    update schedule ("classic" or "lookahead"), an explicit diagonal factor
+    ("lds", "reg" or None for the process default) and an optional rhs (B,N)
     carried through the fused forward solve.
 
     Returns (L, logdet (B,), info (B,), z) with z = L^-1 rhs (None without
-    rhs); the inputs are left untouched. DMOSOPT_CHOL_LOOKAHEAD is latched
-    once per process, so this is how the two schedules are compared inside
-    one process. Native only: a missing extension is an error."""
+    rhs); the inputs are left untouched. DMOSOPT_CHOL_LOOKAHEAD and
+    DMOSOPT_CHOL_FACTOR are latched once per process, so this is how the
+    schedules and the factors are compared inside one process. Native only:
+    a missing extension is an error."""
     if not native_fp32(K):
         raise RuntimeError("chol_factor_multik needs the native extension "
                            "and a float32 GPU tensor")
     L = K.contiguous().clone()
     z = None if rhs is None else rhs.contiguous().float().clone()
     logdet, info = _native.cholesky_multik_sched_(
-        L, z, CHOL_SCHEDULES[schedule])
+        L, z, CHOL_SCHEDULES[schedule], CHOL_FACTORS[factor])
     return L, logdet, info, z
 
 

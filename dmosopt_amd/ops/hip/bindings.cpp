@@ -801,13 +801,17 @@ std::vector<torch::Tensor> cholesky_batched_(torch::Tensor A) {
 // optional rhs (B, N) carried through the fused forward solve.
 // DMOSOPT_CHOL_LOOKAHEAD is latched per process, so this is the only way to
 // compare the two schedules inside one process. In place: A -> L, rhs -> L^-1 rhs.
+// factor picks the panel's diagonal factor the same way (0 = lds, 1 = reg,
+// -1 = the process default latched from DMOSOPT_CHOL_FACTOR).
 std::vector<torch::Tensor> cholesky_multik_sched_(
-    torch::Tensor A, c10::optional<torch::Tensor> rhs, int64_t sched) {
+    torch::Tensor A, c10::optional<torch::Tensor> rhs, int64_t sched,
+    int64_t factor) {
   CHECK_GPU(A);
   TORCH_CHECK(A.dim() == 3 && A.size(1) == A.size(2), "A must be (B, N, N)");
   TORCH_CHECK(A.scalar_type() == torch::kFloat32 && A.is_contiguous(),
               "A must be contiguous float32");
   TORCH_CHECK(sched == 0 || sched == 1, "sched must be 0 or 1");
+  TORCH_CHECK(factor >= -1 && factor <= 1, "factor must be -1, 0 or 1");
   const int B = A.size(0), N = A.size(1);
   float* rhs_ptr = nullptr;
   if (rhs.has_value()) {
@@ -822,7 +826,7 @@ std::vector<torch::Tensor> cholesky_multik_sched_(
   auto info = torch::zeros({B}, A.options().dtype(torch::kInt32));
   launch_cholesky_multik_sched(A.data_ptr<float>(), logdet.data_ptr<float>(),
                                info.data_ptr<int>(), rhs_ptr, B, N, (int)sched,
-                               cur_stream());
+                               (int)factor, cur_stream());
   return {logdet, info};
 }
 
@@ -1705,9 +1709,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "In-place batched Cholesky; returns (logdet, info)");
   m.def("cholesky_multik_sched_", &cholesky_multik_sched_,
         "In-place multi-launch Cholesky with an explicit schedule "
-        "(0 classic, 1 look-ahead) and optional fused rhs; returns "
+        "(0 classic, 1 look-ahead), an explicit diagonal factor (0 lds, "
+        "1 reg, -1 process default) and optional fused rhs; returns "
         "(logdet, info)",
-        py::arg("A"), py::arg("rhs") = py::none(), py::arg("sched") = 0);
+        py::arg("A"), py::arg("rhs") = py::none(), py::arg("sched") = 0,
+        py::arg("factor") = -1);
   m.def("forward_solve_", &forward_solve_, "In-place batched L z = y solve");
   m.def("backward_solve_", &backward_solve_, "In-place batched L^T x = z solve");
   m.def("dominance_degree_matrix", &dominance_degree_matrix);

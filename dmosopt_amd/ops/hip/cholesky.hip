@@ -198,8 +198,19 @@ __global__ __launch_bounds__(CHOL_TPB) void cholesky_batched_kernel(
 // solve + writeback + 3 barriers each); static LDS caps the width at 384
 // (P[384][33] + S + colbuf = 55 KB < 64 KB).
 #define CHOL_PANEL_TPB 384
-// Columns factored per round of the diagonal factor (chol_panel_body).
+// Columns factored per round of the "lds" diagonal factor (chol_panel_body).
 #define CHOL_GROUP_COLS 2
+// Rows of the diagonal-block buffer S: the block plus, as row 32, the rhs
+// segment that rides the "reg" factor.
+#define CHOL_S_ROWS (CHOL_BS + 1)
+// Multipliers fetched per batch of the "reg" factor's rank-1 update.
+#define CHOL_REG_BATCH 8
+
+// v_readlane_b32 at a compile-time lane: one lane's value into a scalar
+// register, no LDS round trip (unlike __shfl = ds_bpermute). Ignores EXEC.
+__device__ __forceinline__ float chol_readlane(float v, int src) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
+}
 #define CHOL_SYRK_TPB 256  // SYRK tile workgroup: 4 waves x 4 sub-tiles
 #define SYRK_TS 64         // trailing-update tile edge
 
@@ -292,6 +303,55 @@ __device__ __forceinline__ void chol_strip_rows(
   }
 }
 
+// The "reg" diagonal factor of chol_panel_body, run by the whole first wave:
+// lane i holds row i of the block in r[], lane 32 (optionally) the rhs
+// segment, every other lane zeros. Right-looking, one column per round, no
+// LDS and no fence on the chain: column j's pivot and multipliers leave the
+// owning lane's register through v_readlane at constant lanes. Per element
+// the fmaf sequence is that of the lds factor (updates in ascending column
+// order, then the true divide), so the factor, and z in row 32, keep every
+// bit. Division and update are UNMASKED: rows above the diagonal collect
+// junk that no lane reads back (multipliers come from lanes t > j only) and
+// that is never written out. The pivot is wave-uniform, so bad (first
+// failing column, 1-based) is tracked as a uniform. Returns the lane's
+// logdet term: lane j ends up holding d_j, so it is one logf per lane after
+// the loop, off the column chain — the same term per lane as the lds factor.
+__device__ __forceinline__ float chol_factor_reg(float (&r)[CHOL_BS], int lane,
+                                                 int bs, int k0, int& bad) {
+  float dj = 1.0f;
+  // Always 32 columns, straight-line: a partial block (bs < 32) arrives
+  // padded with identity rows and columns, whose rounds divide by 1 and
+  // update with zero multipliers. A `j < bs` branch per column instead
+  // turns every r[t] into a phi, and the SLP vectorizer then packs the
+  // update into v_pk_fma_f32 at three v_mov per pair (read the .s).
+#pragma unroll
+  for (int j = 0; j < CHOL_BS; ++j) {
+    float d = chol_readlane(r[j], j);
+    if (d <= 0.0f || !isfinite(d)) {
+      bad = (bad || j >= bs) ? bad : (k0 + j + 1);
+      d = 1e-30f;
+    }
+    d = sqrtf(d);
+    const float q = r[j] / d;
+    r[j] = (lane == j) ? d : q;
+    dj = (lane == j) ? d : dj;
+    // multipliers in batches: back-to-back readlane/fma pairs would each
+    // pay the scalar-write-to-VALU-read wait states
+#pragma unroll
+    for (int t0 = j + 1; t0 < CHOL_BS; t0 += CHOL_REG_BATCH) {
+      float m[CHOL_REG_BATCH];
+#pragma unroll
+      for (int u = 0; u < CHOL_REG_BATCH; ++u)
+        if (t0 + u < CHOL_BS) m[u] = chol_readlane(r[j], t0 + u);
+#pragma unroll
+      for (int u = 0; u < CHOL_REG_BATCH; ++u)
+        if (t0 + u < CHOL_BS) r[t0 + u] = fmaf(-r[j], m[u], r[t0 + u]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  return (lane < bs) ? logf(dj) : 0.0f;
+}
+
 // Factor the 32x32 diagonal block at (k0,k0) and panel-solve the rows below
 // it. One block per matrix; also accumulates the step's logdet contribution
 // deterministically (no atomics: k-steps are stream-ordered).
@@ -306,7 +366,18 @@ __device__ __forceinline__ void chol_strip_rows(
 // then proceeds exactly as the plain panel. Lj ([33][32]) stages the
 // previous panel's rows k0..k0+31 (swizzled) and, in row 32, its solved rhs
 // segment; unused (nullptr) when PRE is false.
-template <bool PRE>
+//
+// REG selects the diagonal factor (DMOSOPT_CHOL_FACTOR, bitwise-identical
+// results, A/B in profiles/README.md):
+//   false ("lds") — 2-column rounds broadcast through colbuf, then a
+//     separate 32-step shuffle solve of the rhs segment after the barrier;
+//   true  ("reg") — column j's pivot and multipliers leave the owning
+//     lane's register through v_readlane at constant lanes, the logdet term
+//     is one logf per lane after the loop, and the rhs segment rides the
+//     factor as row 32 of the bordered block (lane 32, S row 32): dividing
+//     that row by the pivot and giving it the other rows' rank-1 update IS
+//     the forward solve, fmaf for fmaf. colbuf is unused.
+template <bool PRE, bool REG>
 __device__ __forceinline__ void chol_panel_body(
     float* __restrict__ Ab, float* __restrict__ logdet_b,
     int* __restrict__ info_b, int N, int k0, float* __restrict__ rhs_b,
@@ -334,6 +405,10 @@ __device__ __forceinline__ void chol_panel_body(
     for (int idx = tid; idx < bs * bs; idx += blockDim.x)
       S[idx / bs][idx % bs] =
           Ab[(long long)(k0 + idx / bs) * N + k0 + idx % bs];
+    if (REG && rhs_b != nullptr && tid >= CHOL_PANEL_TPB - CHOL_BS) {
+      const int t = tid - (CHOL_PANEL_TPB - CHOL_BS);
+      if (t < bs) S[CHOL_BS][t] = rhs_b[k0 + t];
+    }
     __syncthreads();
   }
   // TRSM staging buffer, declared up front: waves 1+ stage the FIRST chunk
@@ -395,9 +470,12 @@ __device__ __forceinline__ void chol_panel_body(
             S[i][j] = (j <= i) ? adiag[sub][r] - acc[r] : adiag[sub][r];
         }
       }
-      if (rhs_b != nullptr && tid < bs)
-        rhs_b[k0 + tid] = chol_rhs_row_update(Lj[tid], (tid & 7) << 2,
-                                              Lj[CHOL_BS], yv);
+      if (rhs_b != nullptr && tid < bs) {
+        const float yu = chol_rhs_row_update(Lj[tid], (tid & 7) << 2,
+                                             Lj[CHOL_BS], yv);
+        if (REG) S[CHOL_BS][tid] = yu;  // row 32 of the bordered block
+        else rhs_b[k0 + tid] = yu;
+      }
       __threadfence_block();  // S rows cross lanes inside wave 0
     }
   }
@@ -415,12 +493,19 @@ __device__ __forceinline__ void chol_panel_body(
     }
   } else {
     const int lane = tid;
+    // reg: lane 32 is the rhs row whatever bs is; a partial block is padded
+    // to 32 x 32 with the identity and every lane beyond holds zeros
+    // (v_readlane ignores EXEC: nothing it can reach may be uninitialized)
+    const int rhs_lane = (REG && rhs_b != nullptr) ? CHOL_BS : -1;
+    const bool own = lane < bs || lane == rhs_lane;
     float r[CHOL_BS];
 #pragma unroll
     for (int t = 0; t < CHOL_BS; ++t)
-      r[t] = (lane < bs && t < bs) ? S[lane][t] : 0.0f;
+      r[t] = (own && t < bs) ? S[lane][t]
+                             : ((REG && lane == t) ? 1.0f : 0.0f);
     float mylog = 0.0f;
     int bad = 0;
+    if (REG) mylog = chol_factor_reg(r, lane, bs, k0, bad);
     // CHOL_GROUP_COLS columns per round: within the group each column first
     // receives the updates of its in-group predecessors, is factored
     // (shfl pivot + sqrt + div), and broadcast through LDS with ONE
@@ -432,7 +517,7 @@ __device__ __forceinline__ void chol_panel_body(
     // are bit-stable). Groups of 4 and a pure-shuffle factor measured
     // slower: profiles/README.md.
 #pragma unroll
-    for (int g = 0; g < CHOL_BS; g += CHOL_GROUP_COLS) {
+    for (int g = 0; g < (REG ? 0 : CHOL_BS); g += CHOL_GROUP_COLS) {
       if (g >= bs) continue;
 #pragma unroll
       for (int q = 0; q < CHOL_GROUP_COLS; ++q) {
@@ -478,8 +563,8 @@ __device__ __forceinline__ void chol_panel_body(
       }
     }
     // stage the factored block back to LDS (global writeback below is
-    // done coalesced by the whole workgroup)
-    if (lane < bs) {
+    // done coalesced by the whole workgroup); reg: row 32 is the solved z
+    if (own) {
 #pragma unroll
       for (int t = 0; t < CHOL_BS; ++t) {
         if (t >= bs) continue;
@@ -502,7 +587,7 @@ __device__ __forceinline__ void chol_panel_body(
   // factored diagonal block (wave-synchronous, lane j owns entry j; same
   // shuffle scheme as forward_solve_batched_kernel's diagonal solve). The
   // segment already carries the trailing updates of all previous steps.
-  if (rhs_b != nullptr && tid < 64) {
+  if (!REG && rhs_b != nullptr && tid < 64) {
     float* yb = rhs_b + k0;
     const int j = tid;
     float v = (j < bs) ? yb[j] : 0.0f;
@@ -513,6 +598,9 @@ __device__ __forceinline__ void chol_panel_body(
     }
     if (j < bs) yb[j] = v;
   }
+  // reg: z left the factor in S row 32; wave 1 writes it out
+  if (REG && rhs_b != nullptr && tid >= 64 && tid < 64 + bs)
+    rhs_b[k0 + tid - 64] = S[CHOL_BS][tid - 64];
   // factored-block writeback by waves 1+ (concurrent with wave 0's rhs
   // solve above; both only READ S)
   for (int idx = tid - 64; idx >= 0 && idx < bs * bs;
@@ -572,14 +660,15 @@ __device__ __forceinline__ void chol_panel_body(
   }
 }
 
+template <bool REG>
 __global__ __launch_bounds__(CHOL_PANEL_TPB) void chol_panel_kernel(
     float* __restrict__ A, float* __restrict__ logdet, int* __restrict__ info,
     int N, int k0, float* __restrict__ rhs) {
-  __shared__ float S[CHOL_BS][CHOL_BS + 1];
+  __shared__ float S[CHOL_S_ROWS][CHOL_BS + 1];
   __shared__ float colbuf[CHOL_GROUP_COLS][CHOL_BS];
   __shared__ float P[CHOL_PANEL_TPB][CHOL_BS + 1];
   const int b = blockIdx.x;
-  chol_panel_body<false>(A + (long long)b * N * N, logdet + b, info + b, N, k0,
+  chol_panel_body<false, REG>(A + (long long)b * N * N, logdet + b, info + b, N, k0,
                          rhs ? rhs + (long long)b * N : nullptr, S, colbuf, P);
 }
 
@@ -706,11 +795,12 @@ __device__ __forceinline__ void nmll_reduce_body(
 // those of the classic schedule bit for bit (shared inlines above).
 // Role B's tile buffers alias the panel's TRSM buffer P (a block has one
 // role), keeping the static LDS at the panel's ~55 KB + 4 KB for Lj.
+template <bool REG>
 __global__ __launch_bounds__(CHOL_PANEL_TPB) void chol_step_kernel(
     float* __restrict__ A, float* __restrict__ logdet, int* __restrict__ info,
     int N, int k0, float* __restrict__ rhs, float* __restrict__ nmll_out,
     float nmll_c) {
-  __shared__ float S[CHOL_BS][CHOL_BS + 1];
+  __shared__ float S[CHOL_S_ROWS][CHOL_BS + 1];
   __shared__ float colbuf[CHOL_GROUP_COLS][CHOL_BS];
   __shared__ float P[CHOL_PANEL_TPB][CHOL_BS + 1];
   __shared__ float Lj[CHOL_BS + 1][CHOL_BS];  // + the solved rhs segment
@@ -720,14 +810,15 @@ __global__ __launch_bounds__(CHOL_PANEL_TPB) void chol_step_kernel(
   float* Ab = A + (long long)b * N * N;
   float* rhs_b = rhs ? rhs + (long long)b * N : nullptr;
   if (blockIdx.y == 0) {
-    chol_panel_body<true>(Ab, logdet + b, info + b, N, k0, rhs_b, S, colbuf,
-                          P, Lj);
+    chol_panel_body<true, REG>(Ab, logdet + b, info + b, N, k0, rhs_b, S,
+                               colbuf, P, Lj);
     if (nmll_out != nullptr) {
       // NMLL epilogue of the LAST step (no role-B blocks, no trailing rows):
-      // wave 0 has just solved the final rhs segment, so Z[b], logdet[b] and
-      // info[b] are final and this block reduces them itself. The barrier
-      // and fence publish wave 0's global writes to the other waves; the
-      // partials reuse the (idle) TRSM buffer.
+      // the final rhs segment has just been solved and written (by wave 0,
+      // or by wave 1 under the reg factor), so Z[b], logdet[b] and info[b]
+      // are final and this block reduces them itself. The barrier and fence
+      // publish those global writes to the other waves; the partials reuse
+      // the (idle) TRSM buffer.
       __syncthreads();
       __threadfence_block();
       nmll_reduce_body(rhs_b, logdet + b, info + b, nmll_out + b, N, nmll_c,
@@ -894,13 +985,35 @@ static inline void launch_zero_logdet(float* logdet, int B,
                      stream, logdet, B);
 }
 
+// diagonal factor of the panel (chol_panel_body's REG):
+//   lds — 2-column LDS broadcast rounds, separate shuffle solve of the rhs;
+//   reg — register broadcast, deferred logdet, rhs as row 32.
+// DMOSOPT_CHOL_FACTOR=lds/reg selects it, latched once per process; bitwise-
+// identical results, measured A/B in profiles/README.md.
+enum { CHOL_FACTOR_LDS = 0, CHOL_FACTOR_REG = 1 };
+#define CHOL_FACTOR_DEFAULT CHOL_FACTOR_REG
+static inline int chol_factor_default() {
+  static int f = -1;
+  if (f < 0) {
+    const char* e = getenv("DMOSOPT_CHOL_FACTOR");
+    f = e ? (e[0] == 'l' ? CHOL_FACTOR_LDS : CHOL_FACTOR_REG)
+          : CHOL_FACTOR_DEFAULT;
+  }
+  return f;
+}
+
 // Plain panel launch, shared by the classic schedule, panel 0 of the
 // look-ahead schedule and the bf16 path.
 static inline void launch_chol_panel(float* A, float* logdet, int* info,
                                      float* rhs, int B, int N, int k0,
-                                     hipStream_t stream) {
-  hipLaunchKernelGGL(chol_panel_kernel, dim3(B), dim3(CHOL_PANEL_TPB), 0,
-                     stream, A, logdet, info, N, k0, rhs);
+                                     int factor, hipStream_t stream) {
+  if (factor == CHOL_FACTOR_REG)
+    hipLaunchKernelGGL(chol_panel_kernel<true>, dim3(B), dim3(CHOL_PANEL_TPB),
+                       0, stream, A, logdet, info, N, k0, rhs);
+  else
+    hipLaunchKernelGGL(chol_panel_kernel<false>, dim3(B),
+                       dim3(CHOL_PANEL_TPB), 0, stream, A, logdet, info, N,
+                       k0, rhs);
 }
 
 // 64x64 lower-triangle tile pairs of the trailing matrix that starts at r0
@@ -930,9 +1043,10 @@ static inline int chol_lookahead_default() {
 }
 
 static void chol_multik_classic(float* A, float* logdet, int* info,
-                                float* rhs, int B, int N, hipStream_t stream) {
+                                float* rhs, int B, int N, int factor,
+                                hipStream_t stream) {
   for (int k0 = 0; k0 < N; k0 += CHOL_BS) {
-    launch_chol_panel(A, logdet, info, rhs, B, N, k0, stream);
+    launch_chol_panel(A, logdet, info, rhs, B, N, k0, factor, stream);
     const int pairs = chol_tile_pairs(N, k0 + CHOL_BS);
     if (pairs > 0)
       hipLaunchKernelGGL(chol_syrk_kernel, dim3(B, pairs),
@@ -943,32 +1057,40 @@ static void chol_multik_classic(float* A, float* logdet, int* info,
 // nmll_out != nullptr (needs rhs and N > 32): the LAST step launch also
 // reduces the NMLL into nmll_out (B,) — see chol_step_kernel.
 static void chol_multik_lookahead(float* A, float* logdet, int* info,
-                                  float* rhs, int B, int N,
+                                  float* rhs, int B, int N, int factor,
                                   hipStream_t stream,
                                   float* nmll_out = nullptr,
                                   float nmll_c = 0.f) {
-  launch_chol_panel(A, logdet, info, rhs, B, N, 0, stream);
+  launch_chol_panel(A, logdet, info, rhs, B, N, 0, factor, stream);
   for (int k0 = CHOL_BS; k0 < N; k0 += CHOL_BS) {
     // role B covers rows/columns >= k0 + 32; none left on the last steps
     const int pairs = chol_tile_pairs(N, k0 + CHOL_BS);
     const bool last = k0 + CHOL_BS >= N;
-    hipLaunchKernelGGL(chol_step_kernel, dim3(B, 1 + pairs),
-                       dim3(CHOL_PANEL_TPB), 0, stream, A, logdet, info, N,
-                       k0, rhs, last ? nmll_out : (float*)nullptr, nmll_c);
+    float* out = last ? nmll_out : (float*)nullptr;
+    if (factor == CHOL_FACTOR_REG)
+      hipLaunchKernelGGL(chol_step_kernel<true>, dim3(B, 1 + pairs),
+                         dim3(CHOL_PANEL_TPB), 0, stream, A, logdet, info, N,
+                         k0, rhs, out, nmll_c);
+    else
+      hipLaunchKernelGGL(chol_step_kernel<false>, dim3(B, 1 + pairs),
+                         dim3(CHOL_PANEL_TPB), 0, stream, A, logdet, info, N,
+                         k0, rhs, out, nmll_c);
   }
 }
 
-// Explicit-schedule entry (tests and isolated timing compare the two
-// schedules inside one process; the env switch is latched).
+// Explicit-schedule, explicit-factor entry (tests and isolated timing
+// compare the schedules and the factors inside one process; the env switches
+// are latched). factor < 0: the process default.
 extern "C" void launch_cholesky_multik_sched(float* A, float* logdet,
                                              int* info, float* rhs, int B,
-                                             int N, int sched,
+                                             int N, int sched, int factor,
                                              hipStream_t stream) {
+  if (factor < 0) factor = chol_factor_default();
   launch_zero_logdet(logdet, B, stream);
   if (sched == CHOL_SCHED_LOOKAHEAD)
-    chol_multik_lookahead(A, logdet, info, rhs, B, N, stream);
+    chol_multik_lookahead(A, logdet, info, rhs, B, N, factor, stream);
   else
-    chol_multik_classic(A, logdet, info, rhs, B, N, stream);
+    chol_multik_classic(A, logdet, info, rhs, B, N, factor, stream);
 }
 
 extern "C" void launch_cholesky_multik(float* A, float* logdet, int* info,
@@ -977,7 +1099,7 @@ extern "C" void launch_cholesky_multik(float* A, float* logdet, int* info,
   launch_cholesky_multik_sched(
       A, logdet, info, rhs, B, N,
       chol_lookahead_default() ? CHOL_SCHED_LOOKAHEAD : CHOL_SCHED_CLASSIC,
-      stream);
+      -1, stream);
 }
 
 // bf16-SYRK variant of the classic schedule (config-#2 precision route):
@@ -988,7 +1110,8 @@ extern "C" void launch_cholesky_multik_bf16(float* A, float* logdet,
                                             hipStream_t stream) {
   launch_zero_logdet(logdet, B, stream);
   for (int k0 = 0; k0 < N; k0 += CHOL_BS) {
-    launch_chol_panel(A, logdet, info, nullptr, B, N, k0, stream);
+    launch_chol_panel(A, logdet, info, nullptr, B, N, k0,
+                      chol_factor_default(), stream);
     const int pairs = chol_tile_pairs(N, k0 + CHOL_BS);
     if (pairs > 0) launch_chol_syrk_bf16(A, N, k0, pairs, B, stream);
   }
@@ -1037,7 +1160,8 @@ extern "C" void launch_cholesky_nmll_chain(float* A, float* logdet, int* info,
                                            float* rhs, float* out, int B,
                                            int N, float c,
                                            hipStream_t stream) {
-  chol_multik_lookahead(A, logdet, info, rhs, B, N, stream, out, c);
+  chol_multik_lookahead(A, logdet, info, rhs, B, N, chol_factor_default(),
+                        stream, out, c);
 }
 
 extern "C" void launch_cholesky_batched(float* A, float* logdet, int* info,

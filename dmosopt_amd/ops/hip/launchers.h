@@ -26,7 +26,7 @@ void launch_gp_mean_gemv(const float* Ks, const float* alpha, const float* y_mea
 void launch_nmll_reduce(const float* Z, const float* half_logdet, const int* info, float* out, int B,
     int N, float c, hipStream_t stream);
 void launch_cholesky_multik_sched(float* A, float* logdet, int* info, float* rhs, int B, int N,
-    int sched, hipStream_t stream);
+    int sched, int factor, hipStream_t stream);
 void launch_cholesky_multik_bf16(float* A, float* logdet, int* info, int B, int N,
     hipStream_t stream);
 // returns nonzero, launching nothing, when the fused path does not apply
