@@ -93,6 +93,26 @@ class NSGA2Optimizer(MOEA):
             self._di_cache = cache
         return cache
 
+    def _bounds_f32(self, device: torch.device):
+        """The bounds columns as cached float32-contiguous tensors: they are
+        stride-2 views of the (d,2) bounds tensor, and copying them costs two
+        kernels + allocs per generation otherwise."""
+        bc = getattr(self, "_bounds_cache", None)
+        if bc is None or bc[0] != device:
+            lo, hi = (
+                self.state.bounds[:, k].to(device, torch.float32).contiguous() for k in (0, 1)
+            )
+            bc = self._bounds_cache = (device, lo, hi)
+        return bc[1], bc[2]
+
+    def _prefetch(self):
+        """This optimizer's _SpawnPrefetch, made on first use."""
+        if getattr(self, "_spawn_prefetch", None) is None:
+            from dmosopt_amd.moea.variation import _SpawnPrefetch
+
+            self._spawn_prefetch = _SpawnPrefetch()
+        return self._spawn_prefetch
+
     def _x_dists(self, x: torch.Tensor):
         if self.x_distance_fns is None:
             return None
@@ -137,32 +157,17 @@ class NSGA2Optimizer(MOEA):
 
         poolsize = min(poolsize, population.shape[0])
         di_c, di_m = self._di_tensors(population)
-        # bounds columns are stride-2 views of the (d,2) bounds tensor: the
-        # float32-contiguous copies the kernels need are cached (two copy
-        # kernels + allocs per generation otherwise)
-        bc = getattr(self, "_bounds_cache", None)
-        if bc is None or bc[0] != population.device:
-            bc = self._bounds_cache = (
-                population.device,
-                xlb.to(population.device, torch.float32).contiguous(),
-                xub.to(population.device, torch.float32).contiguous(),
-            )
-        xlb_f, xub_f = bc[1], bc[2]
         if population.device.type == "cuda" and ops.native_available():
             # tournament + event-decoded variation chained in ONE binding
             # call (the loop is host-dispatch-bound; the pool tensor never
             # surfaces to python)
-            from dmosopt_amd.moea.variation import (
-                _SpawnPrefetch, spawn_generation_native,
-            )
+            from dmosopt_amd.moea.variation import spawn_generation_native
 
-            pf = getattr(self, "_spawn_prefetch", None)
-            if pf is None:
-                pf = self._spawn_prefetch = _SpawnPrefetch()
             res = spawn_generation_native(
                 population, rank, poolsize, 0.5, rng, popsize,
                 p.crossover_prob, p.mutation_prob, p.mutation_rate,
-                di_c, di_m, xlb_f, xub_f, prefetch=pf, fused=self.gen_fused,
+                di_c, di_m, *self._bounds_f32(population.device),
+                prefetch=self._prefetch(), fused=self.gen_fused,
             )
             if res is not None:
                 x_gen, crossover_indices, mutation_indices = res
@@ -191,45 +196,74 @@ class NSGA2Optimizer(MOEA):
             "mutation_indices": mutation_indices,
         }
 
+    def _count_survivors(self, perm, c_idx, n_children):
+        """Add the surviving crossover pairs and mutation children to the
+        device-side success counters without a host round-trip: children are
+        rows [0, n_children) of the concatenation, so survive where
+        `perm < n_children`."""
+        st = self.state
+        if not isinstance(c_idx, torch.Tensor):
+            c_idx = torch.as_tensor(np.asarray(c_idx), dtype=torch.long, device=perm.device)
+        if (
+            perm.device.type == "cuda"
+            and ops.native_available()
+            and n_children <= 2048
+            and st.successful_crossovers.device.type == "cuda"
+        ):
+            from dmosopt_amd import _hipops
+
+            if _hipops.survivor_count(
+                perm.contiguous(), c_idx.contiguous(), n_children,
+                st.successful_crossovers, st.successful_mutations,
+            ):
+                return
+        # fixed-shape ops only: a boolean gather over the slot-type mask
+        # (masked_select/isin would force a sync or a sort)
+        is_cross = torch.zeros(n_children, dtype=torch.bool, device=perm.device)
+        is_cross[c_idx] = True
+        child = perm < n_children
+        slot = torch.where(child, perm, torch.zeros_like(perm))
+        surv_cross = is_cross[slot] & child
+        st.successful_crossovers += surv_cross.sum() // 2
+        st.successful_mutations += ((~is_cross[slot]) & child).sum()
+
     def update_strategy(self, x_gen, y_gen, gen_state, **params):
-        p = self.opt_params
+        p, st = self.opt_params, self.state
         popsize = p.popsize
+        c_idx = gen_state["crossover_indices"]
+        # (a) select; `counted`: the selection call counted the survivors too
+        counted = False
         if (
             x_gen.device.type == "cuda"
             and self.x_distance_fns is None
             and self.y_distance_metrics == ["crowding"]
             and ops.native_available()
         ):
-            # fused native path: selection + survivor accounting in one
-            # extension call per generation
             from dmosopt_amd import _hipops
 
-            c_idx_acc = gen_state["crossover_indices"]
-            sc = self.state.successful_crossovers
-            sm = self.state.successful_mutations
-            acc_ok = (
-                isinstance(c_idx_acc, torch.Tensor)
-                and c_idx_acc.device.type == "cuda"
-                and sc.device.type == "cuda"
+            select_args = (
+                x_gen.float().contiguous(), y_gen.float().contiguous(),
+                st.population_parm.float().contiguous(),
+                st.population_obj.float().contiguous(), popsize,
+            )
+            # selection + survivor accounting in one extension call where
+            # the count kernel takes the generation (<= 2048 children)
+            counted = (
+                isinstance(c_idx, torch.Tensor)
+                and c_idx.device.type == "cuda"
+                and st.successful_crossovers.device.type == "cuda"
                 and x_gen.shape[0] <= 2048
             )
-            if acc_ok:
+            if counted:
                 parm, obj, rank, perm = _hipops.nsga2_select_acc(
-                    x_gen.float().contiguous(), y_gen.float().contiguous(),
-                    self.state.population_parm.float().contiguous(),
-                    self.state.population_obj.float().contiguous(), popsize,
-                    c_idx_acc.contiguous(), sc, sm, fused=self.gen_fused,
+                    *select_args, c_idx.contiguous(), st.successful_crossovers,
+                    st.successful_mutations, fused=self.gen_fused,
                 )
             else:
-                parm, obj, rank, perm = _hipops.nsga2_select(
-                    x_gen.float().contiguous(), y_gen.float().contiguous(),
-                    self.state.population_parm.float().contiguous(),
-                    self.state.population_obj.float().contiguous(), popsize,
-                    fused=self.gen_fused,
-                )
+                parm, obj, rank, perm = _hipops.nsga2_select(*select_args, fused=self.gen_fused)
         else:
-            population_parm = torch.cat([x_gen, self.state.population_parm], dim=0)
-            population_obj = torch.cat([y_gen, self.state.population_obj], dim=0)
+            population_parm = torch.cat([x_gen, st.population_parm], dim=0)
+            population_obj = torch.cat([y_gen, st.population_obj], dim=0)
             parm, obj, rank, perm = ops.remove_worst(
                 population_parm,
                 population_obj,
@@ -237,37 +271,11 @@ class NSGA2Optimizer(MOEA):
                 x_dists=self._x_dists(population_parm),
                 y_distance_metrics=self.y_distance_metrics,
             )
-        # device-side survivor accounting without a host round-trip: the
-        # generation's children occupy rows [0, n_children) of the
-        # concatenated population, so survival is just `perm < n_children`
-        # plus a boolean gather over the slot-type mask (fixed-shape ops
-        # only — masked_select/isin would force a sync or a sort). The
-        # fused nsga2_select_acc call above already counted (acc_ok).
-        counted = locals().get("acc_ok", False)
-        c_idx = gen_state["crossover_indices"]
-        if not isinstance(c_idx, torch.Tensor):
-            c_idx = torch.as_tensor(np.asarray(c_idx), dtype=torch.long, device=perm.device)
-        n_children = x_gen.shape[0]
-        if not counted and perm.device.type == "cuda" and ops.native_available() and n_children <= 2048:
-            from dmosopt_amd import _hipops
-
-            sc, sm = self.state.successful_crossovers, self.state.successful_mutations
-            if sc.device.type == "cuda":
-                counted = _hipops.survivor_count(
-                    perm.contiguous(), c_idx.contiguous(), n_children, sc, sm
-                )
+        # (b) count survivors
         if not counted:
-            is_cross = torch.zeros(n_children, dtype=torch.bool, device=perm.device)
-            is_cross[c_idx] = True
-            child = perm < n_children
-            slot = torch.where(child, perm, torch.zeros_like(perm))
-            surv_cross = is_cross[slot] & child
-            self.state.successful_crossovers += surv_cross.sum() // 2
-            self.state.successful_mutations += ((~is_cross[slot]) & child).sum()
+            self._count_survivors(perm, c_idx, x_gen.shape[0])
 
-        self.state.population_parm = parm
-        self.state.population_obj = obj
-        self.state.rank = rank
+        st.population_parm, st.population_obj, st.rank = parm, obj, rank
         if parm.shape[0] < popsize and self.logger is not None:
             self.logger.warning(
                 f"NSGA2: population shrank to {parm.shape[0]} (< {popsize})"
@@ -340,23 +348,11 @@ class NSGA2Optimizer(MOEA):
         generation, x_gen rows of all of them, their y_gen rows). Only where
         native_generations_eligible."""
         from dmosopt_amd import _hipops
-        from dmosopt_amd.moea.variation import _SpawnPrefetch
 
         p, st = self.opt_params, self.state
         population = st.population_parm
         di_c, di_m = self._di_tensors(population)
-        bc = getattr(self, "_bounds_cache", None)
-        if bc is None or bc[0] != population.device:
-            xlb, xub = st.bounds[:, 0], st.bounds[:, 1]
-            bc = self._bounds_cache = (
-                population.device,
-                xlb.to(population.device, torch.float32).contiguous(),
-                xub.to(population.device, torch.float32).contiguous(),
-            )
-        pf = getattr(self, "_spawn_prefetch", None)
-        if pf is None:
-            pf = self._spawn_prefetch = _SpawnPrefetch()
-        items = pf.next_chunk(
+        items = self._prefetch().next_chunk(
             self.local_random, p.popsize, p.poolsize, p.crossover_prob,
             p.mutation_prob, population.device, n_gen,
         )
@@ -369,7 +365,8 @@ class NSGA2Optimizer(MOEA):
         x_all, y_all, parm, obj, rank = _hipops.nsga2_run_generations(
             population.contiguous(), st.population_obj.contiguous(),
             st.rank.contiguous(), p.poolsize, 0.5, items[0][6][0], meta,
-            di_c.float().contiguous(), di_m.float().contiguous(), bc[1], bc[2],
+            di_c.float().contiguous(), di_m.float().contiguous(),
+            *self._bounds_f32(population.device),
             float(p.mutation_rate), *mdl.objective.native_mean_args(population.device),
             st.successful_crossovers, st.successful_mutations,
         )

@@ -118,6 +118,17 @@ def _assemble_event_indices(rng, popsize, poolsize, crossover_prob, mutation_pro
     return combined, C, M, seed_sbx, seed_mut
 
 
+def _event_indices_on_device(rng, popsize, poolsize, crossover_prob, mutation_prob, device):
+    """One generation's event indices, drawn and uploaded in a single pinned
+    transfer. Returns (C, M, seed_sbx, seed_mut, (i1, i2, im, ci, mi)): the
+    five lists as views of the one device buffer."""
+    combined, C, M, seed_sbx, seed_mut = _assemble_event_indices(
+        rng, popsize, poolsize, crossover_prob, mutation_prob
+    )
+    views = _to_device_pinned(combined, device).split([C, C, M, 2 * C, M])
+    return C, M, seed_sbx, seed_mut, views
+
+
 class _SpawnPrefetch:
     """Chunked prefetch of the per-generation host randomness.
 
@@ -270,19 +281,12 @@ def spawn_generation_native(
             rng, popsize, poolsize, crossover_prob, mutation_prob,
             population.device,
         )
-        i1_t, i2_t, im_t, c_idx_t, m_idx_t = views
     else:
         seed_t = int(rng.integers(0, 2**62))
-        combined, C, M, seed_sbx, seed_mut = _assemble_event_indices(
-            rng, popsize, poolsize, crossover_prob, mutation_prob
+        C, M, seed_sbx, seed_mut, views = _event_indices_on_device(
+            rng, popsize, poolsize, crossover_prob, mutation_prob, population.device
         )
-        dev = _to_device_pinned(combined, population.device)
-        o = 0
-        i1_t = dev[o : o + C]; o += C
-        i2_t = dev[o : o + C]; o += C
-        im_t = dev[o : o + M]; o += M
-        c_idx_t = dev[o : o + 2 * C]; o += 2 * C
-        m_idx_t = dev[o : o + M]
+    i1_t, i2_t, im_t, c_idx_t, m_idx_t = views
     x_gen = _hipops.generation_spawn(
         population.float().contiguous(), rank.long().contiguous(), poolsize,
         float(p_sel), seed_t, c_idx_t, m_idx_t, i1_t, i2_t, im_t,
@@ -322,21 +326,15 @@ def event_stream_variation(
     # transfer for every index array, staged through a PINNED buffer with a
     # non-blocking copy — a pageable torch.as_tensor(...) H2D blocks the
     # host until the stream drains.
-    combined, C, M, seed_sbx, seed_mut = _assemble_event_indices(
-        rng, popsize, poolsize, crossover_prob, mutation_prob
+    C, M, seed_sbx, seed_mut, views = _event_indices_on_device(
+        rng, popsize, poolsize, crossover_prob, mutation_prob, pool.device
     )
+    i1_t, i2_t, im_t, c_idx_t, m_idx_t = views
     total = 2 * C + M
-    dev = _to_device_pinned(combined, pool.device)
-    o = 0
-    i1_t = dev[o : o + C]; o += C
-    i2_t = dev[o : o + C]; o += C
-    im_t = dev[o : o + M]; o += M
-    c_idx_t = dev[o : o + 2 * C]; o += 2 * C
-    m_idx_t = dev[o : o + M]
 
     if pool.device.type == "cuda" and ops.native_available():
         # whole-generation variation in ONE event-decoded launch: each event
-        # scatters its own child rows, so no host-built src_rows inverse map
+        # scatters its own child rows, so no host-built inverse slot map
         # (bitwise identical values to the split sbx/mutation kernels)
         from dmosopt_amd import _hipops
 

@@ -85,12 +85,12 @@ def _nu_arg(nu) -> float:
 # ------------------------------------------------------------------ ranking
 def pareto_rank(Y: torch.Tensor) -> torch.Tensor:
     if _use_native(Y):
-        # the native binding routes internally: N <= 2048 one-workgroup
-        # bit/LDS peels; N > 2048 the grid-wide COOPERATIVE peel (sync-free
-        # from the host, all CUs; falls back to the chased matvec peel only
-        # if cooperative launch is unavailable). Host syncs in ranking stall
-        # pipelined generation loops far beyond their kernel-time cost
-        # (round-2 lesson, NOTES.md).
+        # the native binding routes internally: N <= 1024 the one-workgroup
+        # bit-matrix peel; N > 1024 the grid-wide COOPERATIVE peel (all CUs).
+        # Both are sync-free from the host, and there is no fallback: a
+        # refused launch raises. Host syncs in ranking stall pipelined
+        # generation loops far beyond their kernel-time cost (round-2
+        # lesson, NOTES.md).
         return _native.pareto_rank(Y.contiguous().float())
     return torch_ref.pareto_rank(Y)
 

@@ -513,36 +513,9 @@ torch::Tensor gp_predict_pof(
   return out;
 }
 
-// Fused SCE-UA CCE stage: candidate proposal and acceptance+resort, one
-// extension call each instead of ~30 torch kernels per stage.
 // Fused tournament selection: stable rank sort + Gumbel top-k weighted
 // sampling without replacement + pool gather in ONE launch. Returns
-// (pool, pool_idx); empty tensors when N exceeds the LDS sort bound.
-// Multi-block tournament (N > the one-workgroup bitonic's sweet spot):
-// Gumbel keys from the SAME Philox stream as tournament_kernel stage 2,
-// sorted with the radix argsort. rank_sorted=true skips the stage-1
-// stable rank sort (nsga2_select emits rank-sorted populations).
-static std::vector<torch::Tensor> tournament_torch(torch::Tensor population,
-                                                   torch::Tensor rank,
-                                                   int64_t poolsize,
-                                                   float log1mp, int64_t seed,
-                                                   bool rank_sorted) {
-  const int N = population.size(0);
-  auto gk = torch::empty({N}, population.options());
-  launch_tournament_keys(gk.data_ptr<float>(), N, log1mp,
-                         (unsigned long long)seed, cur_stream());
-  auto top = torch::argsort(gk, /*dim=*/-1, /*descending=*/true)
-                 .slice(0, 0, poolsize)
-                 .contiguous();
-  torch::Tensor sel = top;
-  if (!rank_sorted) {
-    auto order = torch::argsort(rank, /*stable=*/true, /*dim=*/-1,
-                                /*descending=*/false);
-    sel = order.index_select(0, top).contiguous();
-  }
-  return {population.index_select(0, sel), sel};
-}
-
+// (pool, pool_idx); raises beyond launch_tournament's gate (N <= 2048).
 std::vector<torch::Tensor> tournament_pool(torch::Tensor population,
                                            torch::Tensor rank,
                                            int64_t poolsize, double p_sel,
@@ -559,11 +532,12 @@ std::vector<torch::Tensor> tournament_pool(torch::Tensor population,
   auto pool_idx =
       torch::empty({poolsize}, population.options().dtype(torch::kLong));
   const float log1mp = logf(1.0f - (float)p_sel);
-  if (launch_tournament(population.data_ptr<float>(),
-                        (long long*)rank.data_ptr<int64_t>(), pool.data_ptr<float>(),
-                        (long long*)pool_idx.data_ptr<int64_t>(), N, d, (int)poolsize,
-                        log1mp, (unsigned long long)seed, cur_stream()) != 0)
-    return tournament_torch(population, rank, poolsize, log1mp, seed, false);
+  const int rc = launch_tournament(
+      population.data_ptr<float>(), (long long*)rank.data_ptr<int64_t>(),
+      pool.data_ptr<float>(), (long long*)pool_idx.data_ptr<int64_t>(), N, d,
+      (int)poolsize, log1mp, (unsigned long long)seed, cur_stream());
+  TORCH_CHECK(rc == 0, "tournament_pool: N = ", N,
+              " is beyond the one-workgroup tournament's gate (N <= 2048)");
   return {pool, pool_idx};
 }
 
@@ -583,34 +557,9 @@ bool survivor_count(torch::Tensor perm, torch::Tensor c_idx,
              cur_stream()) == 0;
 }
 
-// Whole-generation variation in one launch (see variation.hip).
-torch::Tensor variation_slots(torch::Tensor pool, torch::Tensor src_rows,
-                              torch::Tensor p1, torch::Tensor p2,
-                              torch::Tensor im, torch::Tensor di_c,
-                              torch::Tensor di_m, torch::Tensor lo,
-                              torch::Tensor hi, double mutation_rate,
-                              int64_t C, int64_t seed_sbx, int64_t seed_mut) {
-  CHECK_GPU(pool);
-  TORCH_CHECK(pool.dtype() == torch::kFloat32 &&
-                  src_rows.dtype() == torch::kLong &&
-                  p1.size(0) == C && p2.size(0) == C,
-              "variation_slots: f32 pool, int64 indices, |p1|=|p2|=C");
-  const int total = src_rows.size(0), d = pool.size(1);
-  auto out = torch::empty({total, d}, pool.options());
-  launch_variation_slots(
-      pool.data_ptr<float>(), (long long*)src_rows.data_ptr<int64_t>(),
-      (long long*)p1.data_ptr<int64_t>(), (long long*)p2.data_ptr<int64_t>(),
-      (long long*)im.data_ptr<int64_t>(), di_c.data_ptr<float>(),
-      di_m.data_ptr<float>(), lo.data_ptr<float>(), hi.data_ptr<float>(),
-      out.data_ptr<float>(), total, (int)C, d, (float)mutation_rate,
-      (unsigned long long)seed_sbx, (unsigned long long)seed_mut,
-      cur_stream());
-  return out;
-}
-
 // Event-decoded whole-generation variation (variation_events_kernel):
-// same child bits as variation_slots, but addressed by the per-event slot
-// lists so the host never materializes the src_rows inverse map.
+// same child bits as sbx_batch + mutation_batch, addressed by the per-event
+// slot lists so the host never materializes an inverse slot-to-child map.
 torch::Tensor variation_events(torch::Tensor pool, torch::Tensor ci,
                                torch::Tensor mi, torch::Tensor p1,
                                torch::Tensor p2, torch::Tensor im,
@@ -639,6 +588,8 @@ torch::Tensor variation_events(torch::Tensor pool, torch::Tensor ci,
   return out;
 }
 
+// Fused SCE-UA CCE stage: candidate proposal and acceptance+resort, one
+// extension call each instead of ~30 torch kernels per stage.
 torch::Tensor sceua_propose(torch::Tensor cx, torch::Tensor lcs,
                             torch::Tensor bl, torch::Tensor bu, int64_t nps,
                             int64_t seed) {
@@ -853,10 +804,13 @@ torch::Tensor dominance_degree_matrix(torch::Tensor Y) {
   return D;
 }
 
-static int COOP_MIN_N = []() {
-  const char* e = getenv("DMOSOPT_COOP_MIN_N");
-  return e ? atoi(e) : 1024;
-}();
+// Route boundary of pareto_rank. N <= COOP_MIN_N takes the one-workgroup
+// bit-matrix peel, whose LDS block is (N*W + W)*4 + (N + 2)*4 bytes with
+// W = ceil(N/32): at N = 1024, W = 32, that is 135,304 bytes, inside the
+// 144 KiB launch_peel_bits allows, and it only shrinks below. Every larger N
+// takes the cooperative peel, which has no size limit. The two routes
+// therefore cover every N >= 1.
+constexpr int COOP_MIN_N = 1024;
 
 torch::Tensor pareto_rank(torch::Tensor Y, int64_t stop = -1) {
   // stop > 0: truncation-selection mode — fronts are peeled only until
@@ -864,82 +818,38 @@ torch::Tensor pareto_rank(torch::Tensor Y, int64_t stop = -1) {
   // rest receive a sentinel rank larger than every true one. Exact for
   // nsga2_select, which discards everything beyond the kept `pop`; the
   // public op default (-1) ranks everything. Only the cooperative path
-  // exploits it — the small-N one-workgroup peels are already ~us-scale.
+  // exploits it — the one-workgroup peel is already ~us-scale.
   CHECK_GPU(Y);
   const int N = Y.size(0), m = Y.size(1);
-  // N > 2048: grid-wide COOPERATIVE peel — sync-free from the host (the
-  // chased matvec path's readback every 16 fronts stalls pipelined
-  // generation loops) and parallel across all CUs (the one-workgroup
-  // peels serialize on one CU: 13.8 ms at N=8192 vs ~0.1-1 ms here)
-  if (N > COOP_MIN_N) {
-    const int W = (N + 31) / 32;
-    auto Yc = Y.contiguous().to(torch::kFloat32);
-    auto opts_i = Y.options().dtype(torch::kInt32);
-    auto Dbits = torch::empty({N, W}, opts_i);
-    auto fmask = torch::empty({3 * W}, opts_i);  // triple-buffered front mask
-    auto n_dom = torch::empty({N}, opts_i);
-    auto ctrl = torch::empty({2}, opts_i);
-    // empty, not zeros: the peel kernels write every rank entry (the fill
-    // kernel cost ~24 us/call at N=3200)
-    auto rank = torch::empty({N}, opts_i);
-    if (launch_coop_peel(Yc.data_ptr<float>(),
-                         (unsigned int*)Dbits.data_ptr<int>(),
-                         (unsigned int*)fmask.data_ptr<int>(),
-                         n_dom.data_ptr<int>(), ctrl.data_ptr<int>(),
-                         rank.data_ptr<int>(), N, m, (int)stop,
-                         cur_stream()) == 0)
-      return rank.to(torch::kLong);
-  }
-  if (N <= 2048) {
-    auto Yc = Y.contiguous().to(torch::kFloat32);
-    auto rank = torch::zeros({N}, Y.options().dtype(torch::kInt32));
-    // bit-matrix path: grid-wide packed dominator build + popcount peel
-    const int W = (N + 31) / 32;
-    const size_t bits_lds = ((size_t)N * W + W) * sizeof(unsigned int) +
-                            (N + 2) * sizeof(int);
-    if (bits_lds <= 144 * 1024) {
-      auto Dbits = torch::empty({N, W}, Y.options().dtype(torch::kInt32));
-      if (launch_peel_bits(Yc.data_ptr<float>(),
-                           (unsigned int*)Dbits.data_ptr<int>(),
-                           rank.data_ptr<int>(), N, m, cur_stream()) == 0)
-        return rank.to(torch::kLong);
-    }
-    // fallback: one-launch peel recomputing dominance from Y in LDS
-    if (launch_peel_from_y(Yc.data_ptr<float>(), rank.data_ptr<int>(), N, m,
-                           cur_stream()) == 0)
-      return rank.to(torch::kLong);
-    auto D = dominance_degree_matrix(Y);
-    launch_peel_single_block(D.data_ptr<int>(), rank.data_ptr<int>(), N, m,
-                             cur_stream());
+  const int W = (N + 31) / 32;
+  auto Yc = Y.contiguous().to(torch::kFloat32);
+  auto opts_i = Y.options().dtype(torch::kInt32);
+  auto Dbits = torch::empty({N, W}, opts_i);
+  // empty, not zeros: both peels write every rank entry (the fill kernel
+  // cost ~24 us/call at N=3200)
+  auto rank = torch::empty({N}, opts_i);
+  if (N <= COOP_MIN_N) {
+    // grid-wide packed dominator build + popcount peel in one workgroup
+    const int rc = launch_peel_bits(Yc.data_ptr<float>(),
+                                    (unsigned int*)Dbits.data_ptr<int>(),
+                                    rank.data_ptr<int>(), N, m, cur_stream());
+    TORCH_CHECK(rc == 0, "pareto_rank: bit-matrix peel refused N = ", N,
+                ", m = ", m, " (LDS block beyond 144 KiB)");
     return rank.to(torch::kLong);
   }
-  auto D = dominance_degree_matrix(Y);
-  auto alive = torch::ones({N}, Y.options().dtype(torch::kUInt8));
-  auto front = torch::empty({N}, Y.options().dtype(torch::kUInt8));
-  auto rank = torch::zeros({N}, Y.options().dtype(torch::kInt32));
-  auto n_front = torch::zeros({1}, Y.options().dtype(torch::kInt32));
-  // Peel in chases of CHASE fronts between host syncs: front k+1 depends
-  // only on device state from commit k, so the launches chain on-stream and
-  // one n_front readback per chase amortizes the sync. Extra launches after
-  // exhaustion are no-ops (alive all zero).
-  constexpr int CHASE = 16;
-  int remaining = N;
-  int k = 0;
-  while (remaining > 0 && k < N + CHASE) {
-    n_front.zero_();
-    for (int c = 0; c < CHASE; ++c) {
-      launch_peel_front(D.data_ptr<int>(), alive.data_ptr<unsigned char>(),
-                        front.data_ptr<unsigned char>(),
-                        n_front.data_ptr<int>(), N, m, cur_stream());
-      launch_commit_front(front.data_ptr<unsigned char>(),
-                          alive.data_ptr<unsigned char>(),
-                          rank.data_ptr<int>(), k + c, N, cur_stream());
-    }
-    const int nf = n_front.item<int>();  // total over the chase; syncs
-    if (nf == 0) break;                  // safety against stalls
-    remaining -= nf;
-    k += CHASE;
-  }
+  // grid-wide COOPERATIVE peel — sync-free from the host and parallel across
+  // all CUs (a one-workgroup peel serializes on one CU: 13.8 ms at N=8192
+  // vs ~0.1-1 ms here)
+  auto fmask = torch::empty({3 * W}, opts_i);  // triple-buffered front mask
+  auto n_dom = torch::empty({N}, opts_i);
+  auto ctrl = torch::empty({2}, opts_i);
+  const int rc = launch_coop_peel(
+      Yc.data_ptr<float>(), (unsigned int*)Dbits.data_ptr<int>(),
+      (unsigned int*)fmask.data_ptr<int>(), n_dom.data_ptr<int>(),
+      ctrl.data_ptr<int>(), rank.data_ptr<int>(), N, m, (int)stop,
+      cur_stream());
+  TORCH_CHECK(rc == 0, "pareto_rank: cooperative launch unavailable or ",
+              "refused at N = ", N, ", m = ", m);
   return rank.to(torch::kLong);
 }
 
@@ -947,37 +857,6 @@ torch::Tensor crowding_distance(torch::Tensor Y) {
   CHECK_GPU(Y);
   const int N = Y.size(0), m = Y.size(1);
   if (N == 1) return torch::ones({1}, Y.options());
-  static int torch_min_n = []() {
-    // default DISABLED: the 10-dispatch torch chain measured 35 ms/epoch
-    // SLOWER end-to-end at pop=1600 than the 208-us single-CU kernel it
-    // replaced (same box) — dispatch cost beats kernel time in the
-    // pipelined loop. Kept selectable for bigger-N re-measurement.
-    const char* e = getenv("DMOSOPT_CROWD_TORCH_MIN_N");
-    return e ? atoi(e) : (1 << 30);
-  }();
-  if (N > torch_min_n) {
-    // the single-workgroup-per-dim LDS bitonic degrades ~N log^2 N on one
-    // CU (208 us at N=3200, m=2); above the gate the multi-block radix
-    // route wins (same arithmetic as ops/torch_ref.crowding_distance)
-    auto lb = std::get<0>(Y.min(0, /*keepdim=*/true));
-    auto ub = std::get<0>(Y.max(0, /*keepdim=*/true));
-    auto span = (ub - lb).clamp_min(0.0);
-    span = torch::where(span == 0, torch::ones_like(span), span);
-    auto U = (Y - lb) / span;
-    auto idx = torch::argsort(U, /*dim=*/0, /*descending=*/false);
-    auto US = torch::gather(U, 0, idx);
-    auto DS = torch::empty_like(US);
-    DS.slice(0, 0, 1).fill_(1.0);
-    DS.slice(0, N - 1, N).fill_(1.0);
-    if (N > 2)
-      DS.slice(0, 1, N - 1) = US.slice(0, 2, N) - US.slice(0, 0, N - 2);
-    // per-column scatter (each column of idx is a permutation) + fixed-
-    // order row sum — scatter_ADD on CUDA floats resolves atomics in
-    // arbitrary order and would break run-to-run bit determinism
-    auto Dm = torch::zeros({N, m}, Y.options());
-    Dm.scatter_(0, idx, DS);
-    return torch::nan_to_num(Dm.sum(1), 0.0);
-  }
   TORCH_CHECK(N <= 16384, "crowding_distance HIP kernel supports N <= 16384");
   auto per_dim = torch::empty({m, N}, Y.options());
   launch_crowding(Y.data_ptr<float>(), per_dim.data_ptr<float>(), N, m,
@@ -1039,6 +918,10 @@ static std::vector<torch::Tensor> nsga2_select_impl(
                     succ_mut->dtype() == torch::kLong && succ_cross->is_cuda() &&
                     succ_mut->is_cuda(),
                 "nsga2_select_acc: int64 GPU tensors required");
+    // survivor_count_kernel's child bitmap holds 2048 slots; larger
+    // generations go through nsga2_select and are counted by the caller
+    TORCH_CHECK(x_gen.size(0) <= 2048, "nsga2_select_acc: ", x_gen.size(0),
+                " children, the survivor count takes at most 2048");
   }
   const long long ng = x_gen.size(0), np_ = pop_parm.size(0);
   const long long dP = x_gen.size(1), dO = y_gen.size(1);
@@ -1124,12 +1007,15 @@ static std::vector<torch::Tensor> nsga2_select_impl(
                  (long long*)rank.data_ptr<int64_t>(), (long long*)perm.data_ptr<int64_t>(),
                  parm_o.data_ptr<float>(), obj_o.data_ptr<float>(),
                  (long long*)rank_o.data_ptr<int64_t>(), P, d, m, cur_stream());
-  if (c_idx)
-    launch_survivor_count(
+  if (c_idx) {
+    const int rc = launch_survivor_count(
         (long long*)perm.data_ptr<int64_t>(),
         (long long*)c_idx->data_ptr<int64_t>(), perm.size(0), c_idx->size(0),
         (int)x_gen.size(0), (long long*)succ_cross->data_ptr<int64_t>(),
         (long long*)succ_mut->data_ptr<int64_t>(), cur_stream());
+    TORCH_CHECK(rc == 0, "nsga2_select_acc: survivor count refused ",
+                x_gen.size(0), " children");
+  }
   return {parm_o, obj_o, rank_o, perm};
 }
 
@@ -1153,30 +1039,27 @@ std::vector<torch::Tensor> nsga2_select_acc(
                            &succ_cross, &succ_mut, fused);
 }
 
-static int gen_tour_torch_min_n() {
-  static int v = []() {
-    const char* e = getenv("DMOSOPT_TOUR_TORCH_MIN_N");
-    return e ? atoi(e) : (1 << 30);
-  }();
-  return v;
-}
-
-// Tournament pool + event-decoded variation chained inside one binding
-// call: the pool tensor never surfaces to python.
+// Tournament pool + event-decoded variation inside one binding call: the
+// pool tensor never surfaces to python. Two routes: the fused kernel (one
+// launch), or tournament launch + variation_events. Beyond
+// launch_tournament's gate (N <= 2048) both return an empty tensor and the
+// caller falls back to the split path. rank_sorted stays in the signature
+// for its callers; no route reads it any more (the tournament kernels detect
+// a rank-sorted population themselves).
 torch::Tensor generation_spawn(
     torch::Tensor population, torch::Tensor rank, int64_t poolsize,
     double p_sel, int64_t seed_t, torch::Tensor ci, torch::Tensor mi,
     torch::Tensor p1, torch::Tensor p2, torch::Tensor im, torch::Tensor di_c,
     torch::Tensor di_m, torch::Tensor lo, torch::Tensor hi,
     double mutation_rate, int64_t seed_sbx, int64_t seed_mut,
-    bool rank_sorted, int64_t fused) {
+    bool /*rank_sorted*/, int64_t fused) {
   CHECK_GPU(population);
   TORCH_CHECK(population.dtype() == torch::kFloat32 &&
                   rank.dtype() == torch::kLong &&
                   poolsize <= population.size(0),
               "generation_spawn: f32 population, int64 rank");
   const int N = population.size(0), d = population.size(1);
-  if (gen_fused(fused) && N <= gen_tour_torch_min_n()) {
+  if (gen_fused(fused)) {
     // ONE launch (spawn_fused_kernel) under launch_tournament's shape gate
     CHECK_GPU(rank);
     const int C = p1.size(0), M = im.size(0);
@@ -1210,12 +1093,6 @@ torch::Tensor generation_spawn(
   auto pool_idx =
       torch::empty({poolsize}, population.options().dtype(torch::kLong));
   const float log1mp = logf(1.0f - (float)p_sel);
-  if (N > gen_tour_torch_min_n()) {
-    auto r = tournament_torch(population, rank, poolsize, log1mp, seed_t,
-                              rank_sorted);
-    return variation_events(r[0].contiguous(), ci, mi, p1, p2, im, di_c,
-                            di_m, lo, hi, mutation_rate, seed_sbx, seed_mut);
-  }
   if (launch_tournament(population.data_ptr<float>(),
                         (long long*)rank.data_ptr<int64_t>(),
                         pool.data_ptr<float>(),
@@ -1649,7 +1526,6 @@ std::vector<torch::Tensor> cholesky_batched_bf16_(torch::Tensor A) {
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("matern_train", &matern_train, "Batched Matern train-kernel assembly");
   m.def("matern_cross", &matern_cross, "Batched Matern cross-kernel assembly");
-  m.def("variation_slots", &variation_slots);
   m.def("variation_events", &variation_events);
   m.def("tournament_pool", &tournament_pool);
   m.def("survivor_count", &survivor_count);

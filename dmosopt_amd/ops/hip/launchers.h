@@ -108,17 +108,13 @@ void launch_sceua_partition_pack(const float* x, const float* xf, const long lon
     int npg, int nopt, hipStream_t stream);
 
 // ---------------------------------------------------------------- pareto.hip
-void launch_peel_single_block(const int* D, int* rank, int N, int m, hipStream_t stream);
+// both peels return nonzero, launching nothing or not the peel, when refused: launch_peel_bits
+// beyond its 144 KiB LDS block, launch_coop_peel when the cooperative launch is not available
 int launch_peel_bits(const float* Y, unsigned int* Dbits_scratch, int* rank, int N, int m,
     hipStream_t stream);
 int launch_coop_peel(const float* Y, unsigned int* Dbits, unsigned int* fmask, int* n_dom, int* ctrl,
     int* rank, int N, int m, int stop, hipStream_t stream);
-int launch_peel_from_y(const float* Y, int* rank, int N, int m, hipStream_t stream);
 void launch_dominance_matrix(const float* Y, int* D, int N, int m, hipStream_t stream);
-void launch_peel_front(const int* D, const unsigned char* alive, unsigned char* front, int* n_front,
-    int N, int m, hipStream_t stream);
-void launch_commit_front(const unsigned char* front, unsigned char* alive, int* rank, int k, int N,
-    hipStream_t stream);
 void launch_crowding(const float* Y, float* out, int N, int m, hipStream_t stream);
 
 // ------------------------------------------------------------- variation.hip
@@ -133,14 +129,8 @@ void launch_variation_events(const float* pool, const long long* ci, const long 
     const float* di_m, const float* lo, const float* hi, float* out, int C, int M, int d,
     float mutation_rate, unsigned long long seed_sbx, unsigned long long seed_mut,
     hipStream_t stream);
-void launch_variation_slots(const float* pool, const long long* src_rows, const long long* p1,
-    const long long* p2, const long long* im, const float* di_c, const float* di_m, const float* lo,
-    const float* hi, float* out, int total, int C, int d, float mutation_rate,
-    unsigned long long seed_sbx, unsigned long long seed_mut, hipStream_t stream);
 
 // -------------------------------------------------------------- moea_ops.hip
-void launch_tournament_keys(float* gkey, int N, float log1mp, unsigned long long seed,
-    hipStream_t stream);
 int launch_tournament(const float* population, const long long* rank, float* pool,
     long long* pool_idx, int N, int d, int poolsize, float log1mp, unsigned long long seed,
     hipStream_t stream);

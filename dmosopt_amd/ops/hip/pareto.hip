@@ -2,14 +2,15 @@
 //
 // Replaces reference dda.py:25-120 and indicators.py:12-51.
 //
-// pareto_rank design (three size regimes, dispatched in bindings.cpp):
-//   N <= ~2048: bit-matrix path — dom_bits_kernel packs "i dominates j"
+// pareto_rank design (two size regimes, dispatched in bindings.cpp, which
+// cover every N between them):
+//   N <= 1024: bit-matrix path — dom_bits_kernel packs "i dominates j"
 //     grid-wide into 32 bits/word, then peel_bits_kernel peels all fronts
 //     in one small block with popcount(dom_mask & front_mask);
-//   fallbacks: single-launch from-Y peel (LDS-staged objectives), and for
-//     large N the DDA matrix (tile-wise, 32-row objective slabs in LDS)
-//     with chased peel_front/commit_front launches or a matvec
-//     dominator-count peel driven from the host.
+//   N > 1024: the same bit matrix kept in global memory and peeled by a
+//     cooperative grid (coop_peel_bits_kernel), grid.sync() per front.
+// dominance_matrix_kernel serves the dominance_degree_matrix op alone
+// (reference dda.py:25-31); no ranking route reads the matrix.
 //
 // crowding design: one workgroup per objective dimension; (value, index)
 // pairs bitonic-sorted in LDS (column min/max read off the sorted ends);
@@ -24,6 +25,10 @@
 #define PTILE 32
 #define PTPB 256
 
+// D[i][j] = number of objectives with Y[i][k] <= Y[j][k], tile-wise with
+// 32-row objective slabs in LDS. Identical rows keep their mutual m (and the
+// diagonal its m), as in the reference: excluding them is a step of the
+// ranking, not part of this matrix.
 __global__ void dominance_matrix_kernel(const float* __restrict__ Y,  // (N, m)
                                         int* __restrict__ D,          // (N, N)
                                         int N, int m) {
@@ -53,179 +58,12 @@ __global__ void dominance_matrix_kernel(const float* __restrict__ Y,  // (N, m)
     }
 }
 
-// Zero mutual-domination entries of identical rows: D[i][j] = 0 where
-// D[i][j] == m and D[j][i] == m (reference dda.py:47-49). Includes the
-// diagonal (a row is always 'identical' to itself) — without this every
-// column max is >= m and no front would ever peel.
-__global__ void zero_identical_kernel(int* __restrict__ D, int N, int m) {
-  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (long long)N * N) return;
-  const int i = (int)(idx / N), j = (int)(idx % N);
-  if (i <= j && D[(long long)i * N + j] == m && D[(long long)j * N + i] == m) {
-    D[(long long)i * N + j] = 0;
-    D[(long long)j * N + i] = 0;
-  }
-}
-
-// One peel pass: for each alive column j compute max_i(D[i][j]) over alive
-// rows; columns with max < m belong to the current front.
-__global__ void peel_front_kernel(const int* __restrict__ D,
-                                  const unsigned char* __restrict__ alive,
-                                  unsigned char* __restrict__ front,  // out
-                                  int* __restrict__ n_front,          // out
-                                  int N, int m) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= N) return;
-  unsigned char f = 0;
-  if (alive[j]) {
-    int mx = -1;
-    const int* col = D + j;
-    for (int i = 0; i < N; ++i)
-      if (alive[i]) mx = max(mx, col[(long long)i * N]);
-    f = (mx < m) ? 1 : 0;
-  }
-  front[j] = f;
-  if (f) atomicAdd(n_front, 1);
-}
-
-__global__ void commit_front_kernel(const unsigned char* __restrict__ front,
-                                    unsigned char* __restrict__ alive,
-                                    int* __restrict__ rank, int k, int N) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= N) return;
-  if (front[j]) {
-    rank[j] = k;
-    alive[j] = 0;
-  }
-}
-
-// Whole peel in ONE launch for N <= PEEL1_NMAX: a single 1024-thread block
-// computes dominator counts once (O(N^2) strided) and then peels fronts
-// with O(front * N) updates per front — replacing ~2 launches per front
-// (~45 us each at low occupancy) with one ~tens-of-us kernel.
-#define PEEL1_NMAX 2048
-#define PEEL1_TPB 1024
-
-__global__ __launch_bounds__(PEEL1_TPB) void peel_single_block_kernel(
-    const int* __restrict__ D,  // (N, N) dominance degrees, identicals zeroed
-    int* __restrict__ rank,     // (N,) out
-    int N, int m) {
-  __shared__ int n_dom[PEEL1_NMAX];
-  __shared__ int front[PEEL1_NMAX];
-  __shared__ int front_sz;
-  __shared__ int remaining;
-  const int tid = threadIdx.x;
-
-  for (int j = tid; j < N; j += PEEL1_TPB) {
-    int cnt = 0;
-    for (int i = 0; i < N; ++i) cnt += (D[(long long)i * N + j] == m) ? 1 : 0;
-    n_dom[j] = cnt;
-  }
-  if (tid == 0) remaining = N;
-  __syncthreads();
-
-  for (int k = 0; remaining > 0 && k <= N; ++k) {
-    if (tid == 0) front_sz = 0;
-    __syncthreads();
-    for (int j = tid; j < N; j += PEEL1_TPB) {
-      if (n_dom[j] == 0) {
-        rank[j] = k;
-        n_dom[j] = -1;  // peeled
-        front[atomicAdd(&front_sz, 1)] = j;
-      }
-    }
-    __syncthreads();
-    const int fs = front_sz;
-    if (fs == 0) break;  // safety
-    // subtract peeled rows' domination counts: threads cover (f, j) pairs
-    for (long long t = tid; t < (long long)fs * N; t += PEEL1_TPB) {
-      const int f = front[t / N];
-      const int j = (int)(t % N);
-      if (n_dom[j] > 0 && D[(long long)f * N + j] == m) atomicSub(&n_dom[j], 1);
-    }
-    __syncthreads();
-    if (tid == 0) remaining -= fs;
-    __syncthreads();
-  }
-}
-
-extern "C" void launch_peel_single_block(const int* D, int* rank, int N, int m,
-                                         hipStream_t stream) {
-  hipLaunchKernelGGL(peel_single_block_kernel, dim3(1), dim3(PEEL1_TPB), 0,
-                     stream, D, rank, N, m);
-}
-
-// Whole ranking from Y in ONE launch: Y (N x m) is staged in LDS and
-// dominance is recomputed on the fly — the (N x N) int32 dominance matrix
-// (640 KB at N=400) never exists, so the single CU running this block does
-// LDS compares instead of pulling the matrix from HBM twice. Semantics
-// identical to dominance_degree_matrix + zero_identical + peel: i dominates
-// j iff all objectives <= and not all equal.
-template <int TPB>
-__global__ __launch_bounds__(TPB) void peel_from_y_kernel(
-    const float* __restrict__ Y, int* __restrict__ rank, int N, int m) {
-  extern __shared__ char sh_raw[];
-  float* Ys = (float*)sh_raw;                 // N * m
-  int* n_dom = (int*)(Ys + (size_t)N * m);    // N
-  int* front = n_dom + N;                     // N
-  int* ctrl = front + N;                      // [front_sz, remaining]
-  const int tid = threadIdx.x;
-
-  for (int i = tid; i < N * m; i += TPB) Ys[i] = Y[i];
-  for (int j = tid; j < N; j += TPB) n_dom[j] = 0;
-  if (tid == 0) ctrl[1] = N;
-  __syncthreads();
-
-  // dominator counts: thread OWNS columns j (register accumulate — no
-  // atomics, no 64-bit div/mod in the pair loop)
-  for (int j = tid; j < N; j += TPB) {
-    int cnt = 0;
-    for (int i = 0; i < N; ++i) {
-      bool le = true, lt = false;
-      for (int t = 0; t < m; ++t) {
-        const float a = Ys[i * m + t], b = Ys[j * m + t];
-        le &= (a <= b);
-        lt |= (a < b);
-      }
-      cnt += (le && lt) ? 1 : 0;
-    }
-    n_dom[j] = cnt;
-  }
-  __syncthreads();
-
-  for (int k = 0; ctrl[1] > 0 && k <= N; ++k) {
-    if (tid == 0) ctrl[0] = 0;
-    __syncthreads();
-    for (int j = tid; j < N; j += TPB) {
-      if (n_dom[j] == 0) {
-        rank[j] = k;
-        n_dom[j] = -1;
-        front[atomicAdd(&ctrl[0], 1)] = j;
-      }
-    }
-    __syncthreads();
-    const int fs = ctrl[0];
-    if (fs == 0) break;
-    // column-owned update: subtract each peeled row's domination of j
-    for (int j = tid; j < N; j += TPB) {
-      if (n_dom[j] <= 0) continue;
-      int dec = 0;
-      for (int q = 0; q < fs; ++q) {
-        const int f = front[q];
-        bool le = true, lt = false;
-        for (int c = 0; c < m; ++c) {
-          const float a = Ys[f * m + c], b = Ys[j * m + c];
-          le &= (a <= b);
-          lt |= (a < b);
-        }
-        dec += (le && lt) ? 1 : 0;
-      }
-      n_dom[j] -= dec;
-    }
-    __syncthreads();
-    if (tid == 0) ctrl[1] -= fs;
-    __syncthreads();
-  }
+extern "C" void launch_dominance_matrix(const float* Y, int* D, int N, int m,
+                                        hipStream_t stream) {
+  dim3 grid((N + PTILE - 1) / PTILE, (N + PTILE - 1) / PTILE);
+  size_t lds_bytes = 2 * PTILE * m * sizeof(float);
+  hipLaunchKernelGGL(dominance_matrix_kernel, grid, dim3(PTPB), lds_bytes,
+                     stream, Y, D, N, m);
 }
 
 // ---------------------------------------------------------------------------
@@ -353,8 +191,8 @@ extern "C" int launch_peel_bits(const float* Y, unsigned int* Dbits_scratch,
 // kernels' capacity (and their one-CU serialization): the packed dominator
 // bit-matrix lives in GLOBAL memory (L2-resident: N=8192 -> 8 MB), every
 // CU participates, and the front-peel loop synchronizes with grid.sync()
-// instead of host readbacks (the chased matvec path's .item() every 16
-// fronts stalls pipelined generation loops — NOTES.md).
+// instead of host readbacks (a readback per batch of fronts stalls
+// pipelined generation loops — NOTES.md).
 #include <hip/hip_cooperative_groups.h>
 
 __global__ __launch_bounds__(256) void coop_peel_bits_kernel(
@@ -475,66 +313,6 @@ extern "C" int launch_coop_peel(const float* Y, unsigned int* Dbits,
       (const void*)coop_peel_bits_kernel, dim3(blocks), dim3(256),
       args, 0, stream);
   return err == hipSuccess ? 0 : -1;
-}
-
-extern "C" int launch_peel_from_y(const float* Y, int* rank, int N, int m,
-                                  hipStream_t stream) {
-  const size_t lds = (size_t)N * m * sizeof(float) + (2 * N + 2) * sizeof(int);
-  if (lds > 144 * 1024) return -1;  // caller falls back to the D-matrix path
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)peel_from_y_kernel<64>,
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
-    hipFuncSetAttribute((const void*)peel_from_y_kernel<256>,
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
-    hipFuncSetAttribute((const void*)peel_from_y_kernel<PEEL1_TPB>,
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
-    attr_set = true;
-  }
-  // a converged population peels into MANY single-digit fronts: the round
-  // loop is then bound by block-barrier latency, which for a 16-wave block
-  // is ~1 us x ~3 barriers x #fronts. A single-wave block makes barriers
-  // ~free; its lower count-pass parallelism only matters for large N.
-  const char* tpb_env = getenv("DMOSOPT_PEEL_TPB");
-  const int tpb = tpb_env ? atoi(tpb_env) : (N <= 1024 ? 256 : PEEL1_TPB);
-  if (tpb <= 64)
-    hipLaunchKernelGGL(peel_from_y_kernel<64>, dim3(1), dim3(64), lds, stream,
-                       Y, rank, N, m);
-  else if (tpb <= 256)
-    hipLaunchKernelGGL(peel_from_y_kernel<256>, dim3(1), dim3(256), lds,
-                       stream, Y, rank, N, m);
-  else
-    hipLaunchKernelGGL(peel_from_y_kernel<PEEL1_TPB>, dim3(1), dim3(PEEL1_TPB),
-                       lds, stream, Y, rank, N, m);
-  return 0;
-}
-
-extern "C" void launch_dominance_matrix(const float* Y, int* D, int N, int m,
-                                        hipStream_t stream) {
-  dim3 grid((N + PTILE - 1) / PTILE, (N + PTILE - 1) / PTILE);
-  size_t lds_bytes = 2 * PTILE * m * sizeof(float);
-  hipLaunchKernelGGL(dominance_matrix_kernel, grid, dim3(PTPB), lds_bytes,
-                     stream, Y, D, N, m);
-  long long total = (long long)N * N;
-  int blocks = (int)((total + 255) / 256);
-  hipLaunchKernelGGL(zero_identical_kernel, dim3(blocks), dim3(256), 0, stream,
-                     D, N, m);
-}
-
-extern "C" void launch_peel_front(const int* D, const unsigned char* alive,
-                                  unsigned char* front, int* n_front, int N,
-                                  int m, hipStream_t stream) {
-  int blocks = (N + 255) / 256;
-  hipLaunchKernelGGL(peel_front_kernel, dim3(blocks), dim3(256), 0, stream, D,
-                     alive, front, n_front, N, m);
-}
-
-extern "C" void launch_commit_front(const unsigned char* front,
-                                    unsigned char* alive, int* rank, int k,
-                                    int N, hipStream_t stream) {
-  int blocks = (N + 255) / 256;
-  hipLaunchKernelGGL(commit_front_kernel, dim3(blocks), dim3(256), 0, stream,
-                     front, alive, rank, k, N);
 }
 
 // ------------------------------------------------------------- crowding

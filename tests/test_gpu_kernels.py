@@ -116,10 +116,10 @@ def test_pareto_rank_matches_reference(dev):
         Y = torch.rand(n, m, generator=g)
         Y[: n // 10] = Y[n // 2 : n // 2 + n // 10]  # inject duplicates
         r_ref = torch_ref.pareto_rank(Y.double())
-        # native column-max peel
+        # native binding (bit-matrix peel at these N)
         r_native = _hipops.pareto_rank(Y.float().to(dev)).cpu()
         assert torch.equal(r_native, r_ref)
-        # dispatched matvec dominator-count peel
+        # the dispatching op
         r_gpu = ops.pareto_rank(Y.float().to(dev)).cpu()
         assert torch.equal(r_gpu, r_ref)
     # many-front stress (d=2 spread points, the TNK-like regime)
@@ -361,7 +361,7 @@ def test_fused_moea_kernels(dev):
 
 
 @pytest.mark.gpu
-def test_variation_slots_matches_split_path(dev):
+def test_variation_events_matches_split_path(dev):
     from dmosopt_amd import _hipops
     from dmosopt_amd import ops as dops
 
@@ -382,12 +382,6 @@ def test_variation_slots_matches_split_path(dev):
     c1, c2 = dops.sbx_from_pool(pool, i1, i2, di_c, lo, hi, seed=s1)
     mm = dops.mutation_from_pool(pool, im, di_m, lo, hi, 0.1, seed=s2)
     want = torch.cat([c1, c2, mm], dim=0)[src_rows]
-
-    got = _hipops.variation_slots(
-        pool.contiguous(), src_rows.contiguous(), i1.contiguous(),
-        i2.contiguous(), im.contiguous(), di_c, di_m, lo, hi, 0.1, C, s1, s2,
-    )
-    assert torch.equal(got, want)
 
     # event-decoded variant (the event_stream_variation route): slot lists
     # partition [0, total); children must land bit-identically
@@ -933,7 +927,7 @@ def test_nmll_graph_matches_eager(dev, monkeypatch):
 
 def test_pareto_rank_large_n_sync_free(dev):
     """N beyond the old 2048 gate (the 8-GPU headline regime: cat pop is
-    1600+1600=3200 rows) must stay on the sync-free single-block peel and
+    1600+1600=3200 rows) must stay on the sync-free cooperative peel and
     match the reference ranking."""
     from dmosopt_amd import ops
     from dmosopt_amd.ops import torch_ref
@@ -970,6 +964,73 @@ def test_pareto_rank_early_stop_truncation_exact(dev):
         # every kept point carries its true rank; sentinel dominates the rest
         assert torch.equal(r_stop[keep_stop], r_full[keep_full]), (n, m, k)
         assert int(r_stop.max()) <= int(r_full.max()) + 1
+
+
+@pytest.mark.parametrize("n", [1024, 1025])
+@pytest.mark.parametrize("m", [2, 3])
+def test_pareto_rank_route_boundary(dev, n, m):
+    """N = 1024 is the last bit-matrix shape (and its largest LDS block),
+    N = 1025 the first cooperative one: both match the float64 reference,
+    and the early-stop peel at 1025 keeps the exact top-k."""
+    from dmosopt_amd import _hipops
+    from dmosopt_amd.ops import torch_ref
+
+    g = torch.Generator().manual_seed(47 + m)
+    Y = torch.rand(n, m, generator=g)
+    Y[: n // 10] = Y[n // 2 : n // 2 + n // 10]  # inject duplicates
+    Yd = Y.float().to(dev)
+    r_full = torch_ref.pareto_rank(Y.double())
+    assert torch.equal(_hipops.pareto_rank(Yd).cpu(), r_full)
+    if n == 1025:
+        k = 512
+        r_stop = _hipops.pareto_rank(Yd, k).cpu()
+        keep_full = torch.argsort(r_full, stable=True)[:k]
+        keep_stop = torch.argsort(r_stop, stable=True)[:k]
+        assert torch.equal(keep_full, keep_stop)
+        assert torch.equal(r_stop[keep_stop], r_full[keep_full])
+        assert int(r_stop.max()) <= int(r_full.max()) + 1
+
+
+@pytest.mark.parametrize("n,m", [(33, 2), (65, 3)])
+def test_dominance_degree_matrix_matches_reference(dev, n, m):
+    """More than one 32-row tile each way, duplicated rows (mutual degree m)
+    and one constant column (every pair counts it)."""
+    from dmosopt_amd import _hipops
+    from dmosopt_amd.ops import torch_ref
+
+    g = torch.Generator().manual_seed(53)
+    Y = torch.rand(n, m, generator=g)
+    Y[: n // 10] = Y[n // 2 : n // 2 + n // 10]
+    Y[:, m - 1] = 0.25
+    D = _hipops.dominance_degree_matrix(Y.to(dev)).cpu()
+    assert torch.equal(D, torch_ref.dominance_degree_matrix(Y))
+
+
+def test_nsga2_select_acc_rejects_more_children_than_it_counts(dev):
+    """The survivor count takes at most 2048 children; beyond, the call
+    raises before any launch and leaves the counters alone."""
+    from dmosopt_amd import _hipops
+
+    ng, npop, d, m = 2049, 8, 3, 2
+    x_gen, y_gen = torch.rand(ng, d, device=dev), torch.rand(ng, m, device=dev)
+    parm, obj = torch.rand(npop, d, device=dev), torch.rand(npop, m, device=dev)
+    c_idx = torch.arange(0, 100, device=dev)
+    sc = torch.full((), 7, dtype=torch.long, device=dev)
+    sm = torch.full((), 11, dtype=torch.long, device=dev)
+    for fused in (0, 1):
+        with pytest.raises(RuntimeError, match="2048"):
+            _hipops.nsga2_select_acc(x_gen, y_gen, parm, obj, npop, c_idx, sc, sm, fused=fused)
+    assert int(sc) == 7 and int(sm) == 11
+
+
+def test_tournament_pool_raises_beyond_gate(dev):
+    from dmosopt_amd import _hipops
+
+    N = 2049
+    population = torch.rand(N, 4, device=dev)
+    rank = torch.zeros(N, dtype=torch.long, device=dev)
+    with pytest.raises(RuntimeError, match="2048"):
+        _hipops.tournament_pool(population, rank, 100, 0.5, 1)
 
 
 def test_transformer_joint_on_gpu(dev):
