@@ -551,7 +551,7 @@ def chol_factor_batched(K):
     return L, logdet, info
 
 
-CHOL_SCHEDULES = {"classic": 0, "lookahead": 1}
+CHOL_SCHEDULES = {"classic": 0, "lookahead": 1, "onelaunch": 2}
 # diagonal factor of the panel; None = the process default
 # (DMOSOPT_CHOL_FACTOR, "reg" unless set to "lds")
 CHOL_FACTORS = {None: -1, "lds": 0, "reg": 1}
@@ -559,9 +559,10 @@ CHOL_FACTORS = {None: -1, "lds": 0, "reg": 1}
 
 def chol_factor_multik(K, rhs=None, schedule="classic", factor=None):
     """Multi-launch factorization of K (B,N,N) with an EXPLICIT trailing-
-    update schedule ("classic" or "lookahead"), an explicit diagonal factor
-    ("lds", "reg" or None for the process default) and an optional rhs (B,N)
-    carried through the fused forward solve.
+    update schedule ("classic", "lookahead", or "onelaunch": the whole
+    factorization in one launch where N fits, else look-ahead), an explicit
+    diagonal factor ("lds", "reg" or None for the process default) and an
+    optional rhs (B,N) carried through the fused forward solve.
 
     Returns (L, logdet (B,), info (B,), z) with z = L^-1 rhs (None without
     rhs); the inputs are left untouched. DMOSOPT_CHOL_LOOKAHEAD and

@@ -748,8 +748,9 @@ std::vector<torch::Tensor> cholesky_batched_(torch::Tensor A) {
 }
 
 // Multi-launch factorization with an EXPLICIT trailing-update schedule
-// (0 = classic panel + SYRK launches, 1 = look-ahead step launches) and an
-// optional rhs (B, N) carried through the fused forward solve.
+// (0 = classic panel + SYRK launches, 1 = look-ahead step launches, 2 = the
+// one-launch kernel where it fits, else look-ahead) and an optional rhs
+// (B, N) carried through the fused forward solve.
 // DMOSOPT_CHOL_LOOKAHEAD is latched per process, so this is the only way to
 // compare the two schedules inside one process. In place: A -> L, rhs -> L^-1 rhs.
 // factor picks the panel's diagonal factor the same way (0 = lds, 1 = reg,
@@ -761,7 +762,7 @@ std::vector<torch::Tensor> cholesky_multik_sched_(
   TORCH_CHECK(A.dim() == 3 && A.size(1) == A.size(2), "A must be (B, N, N)");
   TORCH_CHECK(A.scalar_type() == torch::kFloat32 && A.is_contiguous(),
               "A must be contiguous float32");
-  TORCH_CHECK(sched == 0 || sched == 1, "sched must be 0 or 1");
+  TORCH_CHECK(sched >= 0 && sched <= 2, "sched must be 0, 1 or 2");
   TORCH_CHECK(factor >= -1 && factor <= 1, "factor must be -1, 0 or 1");
   const int B = A.size(0), N = A.size(1);
   float* rhs_ptr = nullptr;

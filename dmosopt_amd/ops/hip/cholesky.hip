@@ -2,8 +2,8 @@
 // forward/backward substitution — the GP fit/predict linear algebra
 // (replaces the LAPACK calls inside sklearn GaussianProcessRegressor,
 // reference model.py:1246-1265). Exact fp32; non-PD pivots clamp and set
-// info[b]. Two right-looking blocked factorizations (BS = 32), chosen by
-// batch count in launch_cholesky_batched:
+// info[b]. Three right-looking blocked factorizations (BS = 32), chosen by
+// batch count and size in launch_cholesky_batched / launch_cholesky_multik:
 //
 // B > CHOL_MULTIK_MAX_B: cholesky_batched_kernel, ONE workgroup (1024
 // threads) per matrix, batch parallelism fills the chip:
@@ -14,9 +14,16 @@
 //     staged in chunk pairs (CHUNK x 32 floats each) so every multiply
 //     reads LDS, with 2x2 register tiles per thread.
 //
-// B <= CHOL_MULTIK_MAX_B: the multi-launch path further down (a 384-thread
+// B <= CHOL_MULTIK_MAX_B, 32 < N <= 615 (both panel buffers inside one CU's
+// LDS): chol_whole_kernel, ONE launch and one workgroup of 16 waves per
+// matrix for the whole factorization — wave 0 runs the serial chain of
+// diagonal factors, the other waves the MFMA trailing update beside it, every
+// hand-off through LDS and block barriers; optionally carrying a fused
+// forward solve and the NMLL reduction.
+//
+// B <= CHOL_MULTIK_MAX_B otherwise: the multi-launch path (a 384-thread
 // panel block per matrix plus 256-thread MFMA SYRK tiles spread over the
-// chip), optionally carrying a fused forward solve.
+// chip, one launch per panel step), with the same optional riders.
 
 #include "common.h"
 #include "launchers.h"
@@ -352,6 +359,27 @@ __device__ __forceinline__ float chol_factor_reg(float (&r)[CHOL_BS], int lane,
   return (lane < bs) ? logf(dj) : 0.0f;
 }
 
+// TRSM of ONE strip row against the factored diagonal block S, in place in
+// LDS: prow <- prow * L11^-T. The row is promoted to registers, so the
+// 512-fmaf chain reads only registers and broadcast S rows. ONE source
+// expression for the panel body and the one-launch kernel (fmaf in ascending
+// t, then the true divide).
+__device__ __forceinline__ void chol_trsm_row(float* prow,
+                                              float (*S)[CHOL_BS + 1]) {
+  float row[CHOL_BS];
+#pragma unroll
+  for (int t = 0; t < CHOL_BS; ++t) row[t] = prow[t];
+#pragma unroll
+  for (int j = 0; j < CHOL_BS; ++j) {
+    float v = row[j];
+#pragma unroll
+    for (int t = 0; t < j; ++t) v = fmaf(-row[t], S[j][t], v);
+    row[j] = v / S[j][j];
+  }
+#pragma unroll
+  for (int t = 0; t < CHOL_BS; ++t) prow[t] = row[t];
+}
+
 // Factor the 32x32 diagonal block at (k0,k0) and panel-solve the rows below
 // it. One block per matrix; also accumulates the step's logdet contribution
 // deterministically (no atomics: k-steps are stream-ordered).
@@ -638,18 +666,7 @@ __device__ __forceinline__ void chol_panel_body(
       // chain then reads only registers and broadcast S rows (the LDS
       // version serializes a ds_read into every fmaf of the chain);
       // identical fmaf order — the solve is bitwise unchanged
-      float row[CHOL_BS];
-#pragma unroll
-      for (int t = 0; t < CHOL_BS; ++t) row[t] = P[tid][t];
-#pragma unroll
-      for (int j = 0; j < CHOL_BS; ++j) {
-        float v = row[j];
-#pragma unroll
-        for (int t = 0; t < j; ++t) v = fmaf(-row[t], S[j][t], v);
-        row[j] = v / S[j][j];
-      }
-#pragma unroll
-      for (int t = 0; t < CHOL_BS; ++t) P[tid][t] = row[t];
+      chol_trsm_row(P[tid], S);
     }
     __syncthreads();
     for (int idx = tid; idx < rows * CHOL_BS; idx += CHOL_PANEL_TPB) {
@@ -831,6 +848,254 @@ __global__ __launch_bounds__(CHOL_PANEL_TPB) void chol_step_kernel(
     tri_tile_decode(blockIdx.y - 1, &ti, &tj);
     chol_syrk_tile_body(Ab, N, k0 - CHOL_BS, k0 + CHOL_BS, ti, tj, rhs_b, Pi,
                         Pj);
+  }
+}
+
+// ------------------------------------------------------ one-launch kernel
+// The WHOLE factorization of one matrix in one workgroup of 16 waves
+// (CHOL_SCHED_ONELAUNCH): the look-ahead schedule's dependency structure
+// with every hand-off inside the workgroup — LDS and two block barriers per
+// panel step, no kernel boundary, no device-scope flag. Per step s
+// (k0 = 32 s), between the two barriers:
+//   wave 0: applies panel s-1's update to diagonal block s and rhs segment s
+//     and factors them (chol_factor_reg, rhs as row 32), operands from LDS;
+//   waves 1..15: write panel s-1 out to global (the output L), then apply
+//     its update as 16x16 MFMA tiles to strip s (rows >= k0 + 32, columns
+//     k0..k0+31; result lands in the TRSM buffer) and to the rest of the
+//     trailing matrix (in place in global / L2) and the rhs rows >= k0 + 32;
+// then, behind the first barrier, the one-row-per-thread TRSM of strip s
+// (chol_trsm_row) while the idle waves write the factored block and z out
+// and stage diagonal block s+1 and its rhs segment from global into LDS for
+// wave 0. The solved strip stays in LDS as panel s: two panel buffers
+// alternate.
+// A 16x16 tile (I, J) of the lower triangle belongs to worker
+// (I (I + 1) / 2 + J) mod 15 for the whole factorization, and so does a
+// 64-row group of the rhs: successive updates of an element are ordered by
+// its owner's program order, hand-offs to wave 0 and the TRSM by the
+// barriers. Element values are those of the other schedules bit for bit:
+// every update goes through chol_subtile_acc / chol_rhs_row_update, whose
+// result does not depend on the tiling or on the operands' LDS layout.
+#define CHOL_WHOLE_TPB 1024
+#define CHOL_WHOLE_WORKERS (CHOL_WHOLE_TPB / 64 - 1)
+// tiles a worker keeps in flight: their global loads are issued together
+#define CHOL_WHOLE_TILE_BATCH 4
+// LDS of one CU (gfx950)
+#define CHOL_CU_LDS_BYTES (160 * 1024)
+
+// S + previous z and next rhs segments + NMLL partials + the next diagonal
+// block + two panel buffers of N - 32 rows
+static inline size_t chol_whole_lds_bytes(int N) {
+  return sizeof(float) *
+         ((size_t)CHOL_S_ROWS * (CHOL_BS + 1) + 2 * CHOL_BS +
+          NMLL_REDUCE_TPB + (size_t)CHOL_BS * (CHOL_BS + 1) +
+          2 * (size_t)(N - CHOL_BS) * (CHOL_BS + 1));
+}
+
+__global__ __launch_bounds__(CHOL_WHOLE_TPB) void chol_whole_kernel(
+    float* __restrict__ A, float* __restrict__ logdet, int* __restrict__ info,
+    int N, float* __restrict__ rhs, float* __restrict__ nmll_out,
+    float nmll_c) {
+  extern __shared__ float whole_lds[];
+  float(*S)[CHOL_BS + 1] = (float(*)[CHOL_BS + 1]) whole_lds;
+  float* zprev = whole_lds + CHOL_S_ROWS * (CHOL_BS + 1);
+  float* ynext = zprev + CHOL_BS;
+  float* part = ynext + CHOL_BS;
+  float(*D)[CHOL_BS + 1] = (float(*)[CHOL_BS + 1])(part + NMLL_REDUCE_TPB);
+  float(*P0)[CHOL_BS + 1] = D + CHOL_BS;
+  float(*P1)[CHOL_BS + 1] = P0 + (N - CHOL_BS);
+  const int b = blockIdx.x;
+  float* Ab = A + (long long)b * N * N;
+  float* rhs_b = rhs ? rhs + (long long)b * N : nullptr;
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int lr = lane & 15, lk = lane >> 4;
+  float ld = 0.0f;  // wave 0, lane 0: logdet, accumulated in step order
+  int inf = 0;      // wave 0, lane 0: first failing column
+  if (wave == 0) {
+    // the serial chain is issue-bound: it goes first on its SIMD
+    __builtin_amdgcn_s_setprio(3);
+    inf = info[b];
+  }
+  // block 0 and its rhs segment, coalesced by the whole workgroup
+  for (int idx = tid; idx < CHOL_BS * CHOL_BS; idx += CHOL_WHOLE_TPB)
+    S[idx / CHOL_BS][idx % CHOL_BS] =
+        Ab[(long long)(idx / CHOL_BS) * N + idx % CHOL_BS];
+  if (rhs_b != nullptr && tid >= CHOL_WHOLE_TPB - CHOL_BS)
+    S[CHOL_BS][tid - (CHOL_WHOLE_TPB - CHOL_BS)] =
+        rhs_b[tid - (CHOL_WHOLE_TPB - CHOL_BS)];
+  __syncthreads();
+
+  for (int k0 = 0, s = 0; k0 < N; k0 += CHOL_BS, ++s) {
+    const int bs = min(CHOL_BS, N - k0);
+    const int rows = N - k0 - CHOL_BS;  // strip rows (<= 0: none)
+    float(*Pcur)[CHOL_BS + 1] = (s & 1) ? P1 : P0;   // strip s -> panel s
+    float(*Pprev)[CHOL_BS + 1] = (s & 1) ? P0 : P1;  // panel s-1: rows k0..N-1
+    if (wave == 0) {
+      if (s > 0) {
+        // diagonal block and rhs segment: panel s-1's update, as in
+        // chol_panel_body<true>; Pprev's first 32 rows are its Lj. Operand
+        // rows past the matrix are clamped: they feed only discarded outputs.
+#pragma unroll
+        for (int sub = 0; sub < 4; ++sub) {
+          const int r16 = (sub >> 1) * 16, c16 = (sub & 1) * 16;
+          const int ra = min(r16 + lr, bs - 1), rb = min(c16 + lr, bs - 1);
+          const f32x4 acc = chol_subtile_acc(Pprev[ra], 0, Pprev[rb], 0, lk);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int i = r16 + lk * 4 + r, j = c16 + lr;
+            const float a = D[i][j];
+            if (i < bs && j < bs) S[i][j] = (j <= i) ? a - acc[r] : a;
+          }
+        }
+        if (rhs_b != nullptr && lane < bs)
+          S[CHOL_BS][lane] =
+              chol_rhs_row_update(Pprev[lane], 0, zprev, ynext[lane]);
+        __threadfence_block();  // S rows cross lanes inside wave 0
+      }
+      // lane 32 is the rhs row; a partial block is padded with the identity
+      const int rhs_lane = (rhs_b != nullptr) ? CHOL_BS : -1;
+      const bool own = lane < bs || lane == rhs_lane;
+      float r[CHOL_BS];
+#pragma unroll
+      for (int t = 0; t < CHOL_BS; ++t)
+        r[t] = (own && t < bs) ? S[lane][t] : ((lane == t) ? 1.0f : 0.0f);
+      int bad = 0;
+      float mylog = chol_factor_reg(r, lane, bs, k0, bad);
+      if (own) {
+#pragma unroll
+        for (int t = 0; t < CHOL_BS; ++t) {
+          if (t >= bs) continue;
+          S[lane][t] = r[t];
+        }
+      }
+      for (int off = 32; off > 0; off >>= 1) {
+        mylog += __shfl_down(mylog, off);
+        const int ob = __shfl_down(bad, off);
+        bad = bad ? bad : ob;
+      }
+      ld += mylog;
+      if (bad && inf == 0) inf = bad;
+    } else if (s == 0) {
+      // strip 0 as it stands
+      for (int idx = tid - 64; idx < rows * CHOL_BS;
+           idx += CHOL_WHOLE_TPB - 64) {
+        const int r = idx / CHOL_BS, c = idx % CHOL_BS;
+        Pcur[r][c] = Ab[(long long)(CHOL_BS + r) * N + c];
+      }
+    } else {
+      const int w = wave - 1;
+      // panel s-1 leaves for global, coalesced
+      for (int idx = tid - 64; idx < (N - k0) * CHOL_BS;
+           idx += CHOL_WHOLE_TPB - 64) {
+        const int r = idx / CHOL_BS, c = idx % CHOL_BS;
+        Ab[(long long)(k0 + r) * N + k0 - CHOL_BS + c] = Pprev[r][c];
+      }
+      // this worker's tiles (I, J), I >= imin, jmin <= J <= I, walked in
+      // steps of 15 along the row-major index of the lower triangle
+      const int jmin = k0 >> 4, imin = jmin + 2;
+      const int ng = (N + 15) >> 4;
+      int I = imin, J = jmin;
+      {
+        const int t0 = imin * (imin + 1) / 2 + jmin;
+        J += (w + CHOL_WHOLE_WORKERS - t0 % CHOL_WHOLE_WORKERS) %
+             CHOL_WHOLE_WORKERS;
+        while (J > I) { J -= I + 1; ++I; }
+      }
+      while (I < ng) {
+        int tI[CHOL_WHOLE_TILE_BATCH], tJ[CHOL_WHOLE_TILE_BATCH];
+#pragma unroll
+        for (int u = 0; u < CHOL_WHOLE_TILE_BATCH; ++u) {
+          while (I < ng && J < jmin) {  // columns of finished panels
+            J += CHOL_WHOLE_WORKERS;
+            while (J > I) { J -= I + 1; ++I; }
+          }
+          tI[u] = I;
+          tJ[u] = J;
+          if (I < ng) {
+            J += CHOL_WHOLE_WORKERS;
+            while (J > I) { J -= I + 1; ++I; }
+          }
+        }
+        float c[CHOL_WHOLE_TILE_BATCH][4];
+#pragma unroll
+        for (int u = 0; u < CHOL_WHOLE_TILE_BATCH; ++u) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int i = tI[u] * 16 + lk * 4 + r, j = tJ[u] * 16 + lr;
+            c[u][r] = (tI[u] < ng && i < N && j < N && j <= i)
+                          ? Ab[(long long)i * N + j]
+                          : 0.0f;
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < CHOL_WHOLE_TILE_BATCH; ++u) {
+          if (tI[u] >= ng) continue;
+          const int ra = min(tI[u] * 16 + lr, N - 1) - k0;
+          const int rb = min(tJ[u] * 16 + lr, N - 1) - k0;
+          const f32x4 acc = chol_subtile_acc(Pprev[ra], 0, Pprev[rb], 0, lk);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int i = tI[u] * 16 + lk * 4 + r, j = tJ[u] * 16 + lr;
+            if (i < N && j < N && j <= i) {
+              const float v = c[u][r] - acc[r];
+              if (tJ[u] < imin) Pcur[i - k0 - CHOL_BS][j - k0] = v;  // strip s
+              else Ab[(long long)i * N + j] = v;
+            }
+          }
+        }
+      }
+      if (rhs_b != nullptr) {
+        for (int g = w; g * 64 < N; g += CHOL_WHOLE_WORKERS) {
+          const int i = g * 64 + lane;
+          if (i >= k0 + CHOL_BS && i < N)
+            rhs_b[i] = chol_rhs_row_update(Pprev[i - k0], 0, zprev, rhs_b[i]);
+        }
+      }
+    }
+    __syncthreads();
+    // TRSM of strip s, one row per thread; the waves it leaves idle write
+    // the factored block and z out and keep z for the next step's updates
+    const int rows_up = rows > 0 ? (rows + 63) & ~63 : 0;
+    if (tid < rows) {
+      chol_trsm_row(Pcur[tid], S);
+    } else if (tid >= rows_up) {
+      const int u = tid - rows_up, nu = CHOL_WHOLE_TPB - rows_up;
+      for (int idx = u; idx < bs * bs; idx += nu) {
+        const int i = idx / bs, t = idx % bs;
+        if (t <= i) Ab[(long long)(k0 + i) * N + k0 + t] = S[i][t];
+      }
+      if (rhs_b != nullptr && u < bs) {
+        const float z = S[CHOL_BS][u];
+        rhs_b[k0 + u] = z;
+        zprev[u] = z;
+      }
+      if (rows > 0) {
+        // the NEXT diagonal block and rhs segment as global holds them
+        // (their last update is in front of the barrier above), staged
+        // coalesced so that wave 0 finds them in LDS: no global latency in
+        // front of the factor
+        const int kn = k0 + CHOL_BS, bn = min(CHOL_BS, N - kn);
+        for (int idx = u; idx < CHOL_BS * CHOL_BS; idx += nu) {
+          const int i = idx / CHOL_BS, j = idx % CHOL_BS;
+          D[i][j] = (i < bn && j < bn) ? Ab[(long long)(kn + i) * N + kn + j]
+                                       : 0.0f;
+        }
+        if (rhs_b != nullptr && u < CHOL_BS)
+          ynext[u] = (u < bn) ? rhs_b[kn + u] : 0.0f;
+      }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    logdet[b] = ld;
+    info[b] = inf;
+  }
+  if (nmll_out != nullptr) {
+    // z, logdet and info are final; the barrier publishes them
+    __syncthreads();
+    __threadfence_block();
+    nmll_reduce_body(rhs_b, logdet + b, info + b, nmll_out + b, N, nmll_c,
+                     part);
   }
 }
 
@@ -1031,7 +1296,11 @@ static inline int chol_tile_pairs(int N, int r0) {
 //                remaining panel (bitwise-identical results).
 // DMOSOPT_CHOL_LOOKAHEAD=1/0 selects it, latched once per process;
 // measured A/B in profiles/README.md.
-enum { CHOL_SCHED_CLASSIC = 0, CHOL_SCHED_LOOKAHEAD = 1 };
+enum {
+  CHOL_SCHED_CLASSIC = 0,
+  CHOL_SCHED_LOOKAHEAD = 1,
+  CHOL_SCHED_ONELAUNCH = 2  // further down
+};
 #define CHOL_LOOKAHEAD_DEFAULT 1
 static inline int chol_lookahead_default() {
   static int la = -1;
@@ -1078,6 +1347,48 @@ static void chol_multik_lookahead(float* A, float* logdet, int* info,
   }
 }
 
+// Up to this batch count the one-block-per-matrix kernel cannot fill the 256
+// CUs, so the multi-launch path wins. DMOSOPT_CHOL_MODE=single|multik
+// overrides the choice for A/B measurement.
+#define CHOL_MULTIK_MAX_B 48
+
+// one-launch schedule: chol_whole_kernel, ONE launch per factorization
+// (grid B), logdet and info written by the kernel itself. It implements the
+// reg factor only and needs more than one panel and both panel buffers
+// inside one CU's LDS (N <= 615); any other request runs the look-ahead
+// schedule. DMOSOPT_CHOL_ONELAUNCH=1/0 (latched once per process) says
+// whether the default routes take it for B <= CHOL_MULTIK_MAX_B; measured
+// A/B in profiles/README.md.
+#define CHOL_ONELAUNCH_DEFAULT 1
+static inline int chol_onelaunch_default() {
+  static int ol = -1;
+  if (ol < 0) {
+    const char* e = getenv("DMOSOPT_CHOL_ONELAUNCH");
+    ol = e ? (e[0] == '1' ? 1 : 0) : CHOL_ONELAUNCH_DEFAULT;
+  }
+  return ol;
+}
+
+static inline bool chol_onelaunch_fits(int N, int factor) {
+  return factor == CHOL_FACTOR_REG && N > CHOL_BS &&
+         chol_whole_lds_bytes(N) <= CHOL_CU_LDS_BYTES;
+}
+
+static void chol_onelaunch(float* A, float* logdet, int* info, float* rhs,
+                           int B, int N, hipStream_t stream,
+                           float* nmll_out = nullptr, float nmll_c = 0.f) {
+  static bool lds_attr_set = false;
+  if (!lds_attr_set) {
+    hipFuncSetAttribute((const void*)chol_whole_kernel,
+                        hipFuncAttributeMaxDynamicSharedMemorySize,
+                        CHOL_CU_LDS_BYTES);
+    lds_attr_set = true;
+  }
+  hipLaunchKernelGGL(chol_whole_kernel, dim3(B), dim3(CHOL_WHOLE_TPB),
+                     chol_whole_lds_bytes(N), stream, A, logdet, info, N, rhs,
+                     nmll_out, nmll_c);
+}
+
 // Explicit-schedule, explicit-factor entry (tests and isolated timing
 // compare the schedules and the factors inside one process; the env switches
 // are latched). factor < 0: the process default.
@@ -1086,6 +1397,13 @@ extern "C" void launch_cholesky_multik_sched(float* A, float* logdet,
                                              int N, int sched, int factor,
                                              hipStream_t stream) {
   if (factor < 0) factor = chol_factor_default();
+  if (sched == CHOL_SCHED_ONELAUNCH) {
+    if (chol_onelaunch_fits(N, factor)) {
+      chol_onelaunch(A, logdet, info, rhs, B, N, stream);
+      return;
+    }
+    sched = CHOL_SCHED_LOOKAHEAD;
+  }
   launch_zero_logdet(logdet, B, stream);
   if (sched == CHOL_SCHED_LOOKAHEAD)
     chol_multik_lookahead(A, logdet, info, rhs, B, N, factor, stream);
@@ -1093,12 +1411,22 @@ extern "C" void launch_cholesky_multik_sched(float* A, float* logdet,
     chol_multik_classic(A, logdet, info, rhs, B, N, factor, stream);
 }
 
+// 1 when the default routes factor (B, N) with the one-launch kernel.
+static inline bool chol_onelaunch_applies(int B, int N) {
+  return chol_onelaunch_default() && chol_lookahead_default() &&
+         B <= CHOL_MULTIK_MAX_B &&
+         chol_onelaunch_fits(N, chol_factor_default());
+}
+
 extern "C" void launch_cholesky_multik(float* A, float* logdet, int* info,
                                        float* rhs, int B, int N,
                                        hipStream_t stream) {
   launch_cholesky_multik_sched(
       A, logdet, info, rhs, B, N,
-      chol_lookahead_default() ? CHOL_SCHED_LOOKAHEAD : CHOL_SCHED_CLASSIC,
+      chol_onelaunch_applies(B, N)
+          ? CHOL_SCHED_ONELAUNCH
+          : (chol_lookahead_default() ? CHOL_SCHED_LOOKAHEAD
+                                      : CHOL_SCHED_CLASSIC),
       -1, stream);
 }
 
@@ -1116,11 +1444,6 @@ extern "C" void launch_cholesky_multik_bf16(float* A, float* logdet,
     if (pairs > 0) launch_chol_syrk_bf16(A, N, k0, pairs, B, stream);
   }
 }
-
-// Up to this batch count the one-block-per-matrix kernel cannot fill the 256
-// CUs, so the multi-launch path wins. DMOSOPT_CHOL_MODE=single|multik
-// overrides the choice for A/B measurement.
-#define CHOL_MULTIK_MAX_B 48
 
 // Factor with the forward solve of rhs (B, N) fused into the multik launch
 // chain. Returns -1 without launching anything when the multik path does not
@@ -1152,16 +1475,21 @@ extern "C" int cholesky_nmll_chain_applies(int B, int N) {
   return chol_fused_solve_applies(B, N) && chol_lookahead_default();
 }
 
-// Look-ahead factor + fused forward solve + NMLL, ceil(N/32) launches and
-// nothing else: the caller's assemble launch has already set rhs = y,
-// logdet = 0 and info = 0 (matern.hip's prologue variant), and the last step
-// launch writes out (B,). Only where cholesky_nmll_chain_applies(B, N).
+// Factor + fused forward solve + NMLL and nothing else: one chol_whole_kernel
+// launch where the one-launch schedule applies, else the look-ahead
+// schedule's ceil(N/32) launches. The caller's assemble launch has already
+// set rhs = y, logdet = 0 and info = 0 (matern.hip's prologue variant), and
+// the last launch writes out (B,). Only where
+// cholesky_nmll_chain_applies(B, N).
 extern "C" void launch_cholesky_nmll_chain(float* A, float* logdet, int* info,
                                            float* rhs, float* out, int B,
                                            int N, float c,
                                            hipStream_t stream) {
-  chol_multik_lookahead(A, logdet, info, rhs, B, N, chol_factor_default(),
-                        stream, out, c);
+  if (chol_onelaunch_applies(B, N))
+    chol_onelaunch(A, logdet, info, rhs, B, N, stream, out, c);
+  else
+    chol_multik_lookahead(A, logdet, info, rhs, B, N, chol_factor_default(),
+                          stream, out, c);
 }
 
 extern "C" void launch_cholesky_batched(float* A, float* logdet, int* info,

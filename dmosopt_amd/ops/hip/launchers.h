@@ -32,8 +32,9 @@ void launch_cholesky_multik_bf16(float* A, float* logdet, int* info, int B, int 
 // returns nonzero, launching nothing, when the fused path does not apply
 int launch_cholesky_fused_solve(float* A, float* logdet, int* info, float* rhs, int B, int N,
     hipStream_t stream);
-// look-ahead factor + fused solve + NMLL in ceil(N/32) launches, after the prologue assemble; only
-// where cholesky_nmll_chain_applies (the shapes and switches of the look-ahead fused-solve route)
+// factor + fused solve + NMLL after the prologue assemble: one launch where the one-launch schedule
+// applies, else the look-ahead schedule's ceil(N/32); only where cholesky_nmll_chain_applies (the
+// shapes and switches of the look-ahead fused-solve route)
 int cholesky_nmll_chain_applies(int B, int N);
 void launch_cholesky_nmll_chain(float* A, float* logdet, int* info, float* rhs, float* out, int B,
     int N, float c, hipStream_t stream);
