@@ -40,6 +40,7 @@ sampler_registry = {
 
 optimizer_registry = {
     "nsga2": "dmosopt_amd.moea.nsga2.NSGA2Optimizer",
+    "nsga3": "dmosopt_amd.moea.nsga3.NSGA3Optimizer",
     "age": "dmosopt_amd.moea.agemoea.AGEMOEAOptimizer",
     "smpso": "dmosopt_amd.moea.smpso.SMPSOOptimizer",
     "cmaes": "dmosopt_amd.moea.cmaes.CMAESOptimizer",

@@ -177,6 +177,40 @@ def remove_worst(
     return population_parm[perm], population_obj[perm], rank[:pop], perm
 
 
+def nsga3_select_native(x_gen, y_gen, pop_parm, pop_obj, Z) -> bool:
+    """The gate of the native NSGA-III selection: float32 GPU populations on
+    the native path and a shape ``_hipops.nsga3_select_fits`` admits."""
+    return native_fp32(x_gen, y_gen, pop_parm, pop_obj) and _native.nsga3_select_fits(
+        y_gen.shape[0] + pop_obj.shape[0], Z.shape[0], y_gen.shape[1]
+    )
+
+
+def nsga3_select(x_gen, y_gen, pop_parm, pop_obj, keep, Z, dir_prio, row_prio):
+    """NSGA-III survivor selection of the merged rows ``[x_gen; pop_parm]``
+    against the reference directions ``Z`` (H, m): Pareto rank, ideal and
+    intercept normalisation, association to the nearest direction, niching
+    with the tie priorities ``dir_prio`` (H,) / ``row_prio`` (N,) (permutations,
+    lower = earlier). Stateless; non-finite objectives are out of scope.
+
+    Returns (parm, obj, rank, perm, ideal, scale, niche, dist): the rows kept
+    (min(keep, N) of them), their index ``perm`` into the merged rows, and for
+    inspection the ideal point, the scale and every merged row's direction and
+    distance (-1 / +inf outside the fronts admitted). Float32 GPU tensors
+    inside the gate run ops/hip/nsga3.hip; everything else
+    torch_ref.nsga3_select in the objectives' dtype, on their device."""
+    if nsga3_select_native(x_gen, y_gen, pop_parm, pop_obj, Z):
+        return tuple(_native.nsga3_select(
+            x_gen.contiguous(), y_gen.contiguous(),
+            pop_parm.contiguous(), pop_obj.contiguous(), int(keep),
+            Z.float().contiguous(), dir_prio.contiguous(), row_prio.contiguous(),
+        ))
+    parm = torch.cat([x_gen, pop_parm], dim=0)
+    obj = torch.cat([y_gen, pop_obj], dim=0)
+    return torch_ref.nsga3_select(
+        parm, obj, keep, Z.to(obj.dtype), dir_prio, row_prio, rank=pareto_rank(obj)
+    )
+
+
 def top_k_mo(x: torch.Tensor, y: torch.Tensor, top_k=None):
     """Top-k rows by non-dominated sort (reference MOEA.top_k_MO,
     MOEA.py:350-372); returns (x, y) unchanged when top_k is not an int or
@@ -605,6 +639,7 @@ __all__ = [
     "euclidean_distance_metric",
     "order_mo",
     "remove_worst",
+    "nsga3_select",
     "top_k_mo",
     "get_duplicates",
     "remove_duplicates",

@@ -1040,6 +1040,78 @@ std::vector<torch::Tensor> nsga2_select_acc(
                            &succ_cross, &succ_mut, fused);
 }
 
+// NSGA-III survivor selection (ops/hip/nsga3.hip): merged rows [x_gen;
+// pop_parm], the existing peel for the rank, then normalise, associate and
+// niche + gather: no host sync. Returns (parm, obj, rank, perm, ideal,
+// scale, niche, dist); niche / dist cover all ng + np merged rows (-1 / +inf
+// outside the fronts admitted).
+bool nsga3_select_fits_py(int64_t N, int64_t H, int64_t m) {
+  return N <= INT_MAX && H <= INT_MAX && m <= INT_MAX &&
+         nsga3_select_fits((int)N, (int)H, (int)m) != 0;
+}
+
+std::vector<torch::Tensor> nsga3_select(
+    torch::Tensor x_gen, torch::Tensor y_gen, torch::Tensor pop_parm,
+    torch::Tensor pop_obj, int64_t keep, torch::Tensor Z,
+    torch::Tensor dir_prio, torch::Tensor row_prio) {
+  const char* fn = "nsga3_select";
+  gp_check_f32(fn, "x_gen", x_gen);
+  gp_check_f32(fn, "y_gen", y_gen);
+  gp_check_f32(fn, "pop_parm", pop_parm);
+  gp_check_f32(fn, "pop_obj", pop_obj);
+  gp_check_f32(fn, "Z", Z);
+  CHECK_GPU(dir_prio);
+  CHECK_GPU(row_prio);
+  TORCH_CHECK(x_gen.dim() == 2 && y_gen.dim() == 2 && pop_parm.dim() == 2 &&
+                  pop_obj.dim() == 2 && Z.dim() == 2 &&
+                  x_gen.size(1) == pop_parm.size(1) &&
+                  y_gen.size(1) == pop_obj.size(1) &&
+                  x_gen.size(0) == y_gen.size(0) &&
+                  pop_parm.size(0) == pop_obj.size(0) &&
+                  Z.size(1) == y_gen.size(1) && keep >= 1,
+              "nsga3_select: shape mismatch");
+  const int64_t ng = x_gen.size(0), np_ = pop_parm.size(0), N = ng + np_;
+  const int64_t dP = x_gen.size(1), dO = y_gen.size(1), H = Z.size(0);
+  TORCH_CHECK(dP >= 1 && nsga3_select_fits_py(N, H, dO), "nsga3_select: N = ",
+              N, ", H = ", H, ", m = ", dO, " outside nsga3_select_fits");
+  TORCH_CHECK(dir_prio.scalar_type() == torch::kLong && dir_prio.dim() == 1 &&
+                  dir_prio.size(0) == H &&
+                  row_prio.scalar_type() == torch::kLong &&
+                  row_prio.dim() == 1 && row_prio.size(0) == N,
+              "nsga3_select: dir_prio (H,) and row_prio (N,) must be int64");
+  const int64_t K = std::min<int64_t>(keep, N);
+  auto obj = torch::empty({N, dO}, y_gen.options());
+  launch_cat_rows(y_gen.data_ptr<float>(), pop_obj.data_ptr<float>(),
+                  obj.data_ptr<float>(), ng * dO, N * dO, cur_stream());
+  auto rank = pareto_rank(obj, -1);  // (N,) long, every front
+  auto lopt = x_gen.options().dtype(torch::kLong);
+  auto iopt = x_gen.options().dtype(torch::kInt32);
+  auto ctrl = torch::empty({4}, iopt);
+  auto rho = torch::empty({H}, iopt);
+  auto ideal = torch::empty({dO}, y_gen.options());
+  auto scale = torch::empty({dO}, y_gen.options());
+  auto niche = torch::empty({N}, lopt);
+  auto dist = torch::empty({N}, y_gen.options());
+  auto parm_o = torch::empty({K, dP}, x_gen.options());
+  auto obj_o = torch::empty({K, dO}, y_gen.options());
+  auto rank_o = torch::empty({K}, lopt);
+  auto perm = torch::empty({K}, lopt);
+  const int rc = launch_nsga3_select(
+      x_gen.data_ptr<float>(), pop_parm.data_ptr<float>(),
+      obj.data_ptr<float>(), (const long long*)rank.data_ptr<int64_t>(),
+      Z.data_ptr<float>(), (const long long*)dir_prio.data_ptr<int64_t>(),
+      (const long long*)row_prio.data_ptr<int64_t>(), (int)ng, (int)np_,
+      (int)dP, (int)dO, (int)H, (int)K, ctrl.data_ptr<int>(),
+      rho.data_ptr<int>(), ideal.data_ptr<float>(), scale.data_ptr<float>(),
+      (long long*)niche.data_ptr<int64_t>(), dist.data_ptr<float>(),
+      parm_o.data_ptr<float>(), obj_o.data_ptr<float>(),
+      (long long*)rank_o.data_ptr<int64_t>(),
+      (long long*)perm.data_ptr<int64_t>(), cur_stream());
+  TORCH_CHECK(rc == 0, "nsga3_select: launcher refused its gate");
+  gp_check_launch(fn, "selection");
+  return {parm_o, obj_o, rank_o, perm, ideal, scale, niche, dist};
+}
+
 // Tournament pool + event-decoded variation inside one binding call: the
 // pool tensor never surfaces to python. Two routes: the fused kernel (one
 // launch), or tournament launch + variation_events. Beyond
@@ -1546,6 +1618,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("nsga2_select_acc", &nsga2_select_acc, py::arg("x_gen"), py::arg("y_gen"),
         py::arg("pop_parm"), py::arg("pop_obj"), py::arg("pop"), py::arg("c_idx"),
         py::arg("succ_cross"), py::arg("succ_mut"), py::arg("fused") = -1);
+  m.def("nsga3_select", &nsga3_select,
+        "NSGA-III survivor selection (cat+rank+normalise+associate+niche+gather)",
+        py::arg("x_gen"), py::arg("y_gen"), py::arg("pop_parm"), py::arg("pop_obj"),
+        py::arg("keep"), py::arg("Z"), py::arg("dir_prio"), py::arg("row_prio"));
+  m.def("nsga3_select_fits", &nsga3_select_fits_py, py::arg("N"), py::arg("H"),
+        py::arg("m"));
   m.def("gen_fused_default", &gen_fused_default,
         "False under DMOSOPT_GEN_FUSED=0: the generation loop's chains of launches");
   m.def("nsga2_generations_fit", &nsga2_generations_fit);

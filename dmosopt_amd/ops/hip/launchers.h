@@ -167,6 +167,20 @@ void launch_cat_rows(const float* a, const float* b, float* out, long long na_el
     long long total_elems, hipStream_t stream);
 void launch_colsum(const float* per_dim, float* out, int m, int N, hipStream_t stream);
 
+// ----------------------------------------------------------------- nsga3.hip
+// NSGA-III survival after the peel: normalise (one workgroup), associate (grid-wide), niche +
+// gather (one workgroup). Y (ng + np, m) is [y_gen; pop_obj], rank its Pareto rank, K <= ng + np
+// the rows kept. ctrl (4,) int32 and rho (H,) int32 are scratch the first launch initialises.
+// 1 where the shape is inside the kernels' LDS blocks (N <= 4096, H <= 2048, m <= 16, and the
+// dynamic block the niche kernel asks for within the limit the launcher sets); the launcher
+// returns -1, launching nothing, outside it.
+int nsga3_select_fits(int N, int H, int m);
+int launch_nsga3_select(const float* x_gen, const float* pop_parm, const float* Y,
+    const long long* rank, const float* Z, const long long* dir_prio, const long long* row_prio,
+    int ng, int np, int d, int m, int H, int K, int* ctrl, int* rho, float* ideal, float* scale,
+    long long* niche, float* dist, float* parm_o, float* obj_o, long long* rank_o,
+    long long* perm, hipStream_t stream);
+
 // ------------------------------------------------------ agemoea_survival.hip
 void launch_agemoea_survival(const float* D, const unsigned char* preselected, float* crowd, int m,
     hipStream_t s);

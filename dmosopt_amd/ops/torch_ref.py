@@ -607,3 +607,158 @@ def mean_in_column_order(P: Tensor) -> Tensor:
     for b in range(1, P.shape[1]):
         s += P[:, b]
     return s / torch.full_like(s, P.shape[1])
+
+
+# ------------------------------------------------------------------ NSGA-III
+# Reference-direction survival (Deb & Jain 2014), stateless per call; the
+# contract of ops/hip/nsga3.hip, in the dtype of the objectives. Every function
+# but nsga3_niche_sequential is fixed-shape tensor code without a host sync.
+# Non-finite objectives are out of scope.
+def nsga3_level(rank: Tensor, keep: int) -> Tensor:
+    """The last front admitted: the smallest l with #{rank <= l} >= min(keep,
+    N), as a 0-d long tensor. S = {rank <= l}, P = {rank < l}, F = {rank == l}."""
+    n = rank.shape[0]
+    counts = torch.zeros(n, dtype=torch.long, device=rank.device)
+    counts.scatter_add_(0, rank.clamp(0, n - 1), torch.ones_like(rank))
+    # the cumulative counts ascend: the entries below K come before front l
+    return (counts.cumsum(0) < min(int(keep), n)).sum()
+
+
+def nsga3_normalize(Y: Tensor, rank: Tensor, keep: int):
+    """(ideal (m,), scale (m,), l): ideal the column minimum over S; scale the
+    hyperplane intercepts through the ASF extremes of the first front
+    (weights 1 on the axis, 1e-6 off it, ties to the lowest row), solved in
+    double; the first front's column maximum of Y - ideal where two extremes
+    coincide or the solve is singular or not positive; 1 where that is below
+    1e-6."""
+    n, m = Y.shape
+    dt, dev = Y.dtype, Y.device
+    l = nsga3_level(rank, keep)
+    in_S, in_F0 = rank <= l, rank == 0
+    inf = torch.full_like(Y, float("inf"))
+    ideal = torch.where(in_S[:, None], Y, inf).min(dim=0).values
+    T = Y - ideal
+    w = torch.full((m, m), 1e-6, dtype=dt, device=dev)
+    w.fill_diagonal_(1.0)
+    asf = (T[:, None, :] / w[None, :, :]).max(dim=2).values  # [row, axis]
+    ext = torch.where(in_F0[:, None], asf, inf).argmin(dim=0)  # first minimum
+    E = T[ext].to(torch.float64)
+    a, info = torch.linalg.solve_ex(E, torch.ones(m, 1, dtype=torch.float64, device=dev))
+    a = a[:, 0]
+    same = (ext[:, None] == ext[None, :]) & ~torch.eye(m, dtype=torch.bool, device=dev)
+    ok = ~same.any() & (info == 0) & torch.isfinite(a).all() & (a > 0).all()
+    fallback = torch.where(in_F0[:, None], T, -inf).max(dim=0).values
+    scale = torch.where(ok, (1.0 / a).to(dt), fallback)
+    scale = torch.where(scale >= 1e-6, scale, torch.ones_like(scale))
+    return ideal, scale, l
+
+
+def nsga3_associate(Y: Tensor, ideal: Tensor, scale: Tensor, Z: Tensor, in_S: Tensor):
+    """(niche (N,) long, dist (N,)): the direction nearest to each normalised
+    row by perpendicular distance, ties to the lowest direction, and that
+    distance, formed from the residual y' - (y'.z)z component by component.
+    Rows outside ``in_S`` hold -1 / +inf."""
+    yp = (Y - ideal) / scale
+    Zt = Z.to(Y.dtype)
+    zh = Zt / Zt.square().sum(dim=1, keepdim=True).sqrt()
+    n, (H, m) = Y.shape[0], zh.shape
+    niche = torch.empty(n, dtype=torch.long, device=Y.device)
+    dist = torch.empty(n, dtype=Y.dtype, device=Y.device)
+    step = max(1, (1 << 22) // (H * m))  # rows per (rows, H, m) block
+    for i0 in range(0, n, step):
+        y = yp[i0:i0 + step]
+        dot = (y[:, None, :] * zh[None, :, :]).sum(dim=2)
+        res = y[:, None, :] - dot[:, :, None] * zh[None, :, :]
+        d = res.square().sum(dim=2).sqrt()
+        h = d.argmin(dim=1)  # first minimum
+        niche[i0:i0 + step] = h
+        dist[i0:i0 + step] = d.gather(1, h[:, None])[:, 0]
+    niche = torch.where(in_S, niche, torch.full_like(niche, -1))
+    dist = torch.where(in_S, dist, torch.full_like(dist, float("inf")))
+    return niche, dist
+
+
+def nsga3_niche_sequential(rank, niche, dist, keep, H, dir_prio, row_prio) -> Tensor:
+    """The textbook niching loop on the host, the oracle of nsga3_niche: P in
+    (rank, index) order, then R times the direction with a candidate left and
+    the smallest (niche count, dir_prio), its (dist, index)-minimal candidate
+    while the count is zero and its row_prio-minimal one after that."""
+    r, pi, d = rank.tolist(), niche.tolist(), dist.tolist()
+    dp, rp = dir_prio.tolist(), row_prio.tolist()
+    n = len(r)
+    K = min(int(keep), n)
+    l = 0
+    while sum(1 for v in r if v <= l) < K:
+        l += 1
+    P = sorted((i for i in range(n) if r[i] < l), key=lambda i: (r[i], i))
+    rho = [0] * H
+    for i in P:
+        rho[pi[i]] += 1
+    cand = {}
+    for i in range(n):
+        if r[i] == l:
+            cand.setdefault(pi[i], []).append(i)
+    picks = []
+    for _ in range(K - len(P)):
+        h = min(cand, key=lambda h: (rho[h], dp[h]))
+        if rho[h] == 0:
+            i = min(cand[h], key=lambda i: (d[i], i))
+        else:
+            i = min(cand[h], key=lambda i: rp[i])
+        cand[h].remove(i)
+        if not cand[h]:
+            del cand[h]  # exhausted: out of the race
+        rho[h] += 1
+        picks.append(i)
+    return torch.tensor(P + picks, dtype=torch.long, device=rank.device)
+
+
+def _segment_heads(sorted_keys: Tensor) -> Tensor:
+    head = torch.ones_like(sorted_keys, dtype=torch.bool)
+    head[1:] = sorted_keys[1:] != sorted_keys[:-1]
+    return head
+
+
+def nsga3_niche(rank, niche, dist, keep, H, dir_prio, row_prio) -> Tensor:
+    """nsga3_niche_sequential in closed form. Each direction's candidates are
+    listed: the (dist, index)-minimal one first where the initial niche count
+    rho_h is 0, the others by row_prio. The candidate at position t gets the
+    key (rho_h + t) H + dir_prio[h]; picking h raises rho_h alone, so the
+    loop serves every direction at count c, in dir_prio order, before any at
+    c + 1, and its picks are the R smallest keys in key order."""
+    n = rank.shape[0]
+    dev = rank.device
+    K = min(int(keep), n)
+    ar = torch.arange(n, device=dev)
+    l = nsga3_level(rank, keep)
+    in_P, in_F = rank < l, rank == l
+    pi = niche.clamp(0, H - 1)
+    rho = torch.zeros(H, dtype=torch.long, device=dev).scatter_add_(0, pi, in_P.long())
+    seg = torch.where(in_F, pi, torch.full_like(pi, H))  # non-candidates last
+    o = lexsort([dist, seg])  # by (direction, dist, index)
+    is_first = torch.zeros(n, dtype=torch.bool, device=dev)
+    is_first[o] = _segment_heads(seg[o])
+    is_first &= in_F & (rho[pi] == 0)
+    o = lexsort([row_prio, (~is_first).long(), seg])  # list order
+    head = _segment_heads(seg[o])
+    start = torch.cummax(torch.where(head, ar, torch.zeros_like(ar)), dim=0).values
+    t = torch.empty_like(ar)
+    t[o] = ar - start
+    key = torch.where(
+        in_F, (1 << 40) + (rho[pi] + t) * H + dir_prio[pi],
+        torch.where(in_P, rank * n + ar,
+                    torch.full_like(ar, torch.iinfo(torch.long).max)))
+    return torch.argsort(key, stable=True)[:K]
+
+
+def nsga3_select(parm, obj, keep, Z, dir_prio, row_prio, rank=None):
+    """NSGA-III survival of the rows (parm, obj): (parm, obj, rank, perm,
+    ideal, scale, niche, dist) with perm (min(keep, N),) the rows kept, P
+    first in (rank, index) order, then the picks in pick order; niche / dist
+    over all N rows. ``rank``: the Pareto rank of obj where the caller has it."""
+    if rank is None:
+        rank = pareto_rank(obj)
+    ideal, scale, l = nsga3_normalize(obj, rank, keep)
+    niche, dist = nsga3_associate(obj, ideal, scale, Z, rank <= l)
+    perm = nsga3_niche(rank, niche, dist, keep, Z.shape[0], dir_prio, row_prio)
+    return parm[perm], obj[perm], rank[perm], perm, ideal, scale, niche, dist

@@ -38,6 +38,7 @@ ext = CUDAExtension(
         os.path.join("dmosopt_amd", "ops", "hip", "gp_mean_grad.hip"),
         os.path.join("dmosopt_amd", "ops", "hip", "gp_path.hip"),
         os.path.join("dmosopt_amd", "ops", "hip", "gp_pof.hip"),
+        os.path.join("dmosopt_amd", "ops", "hip", "nsga3.hip"),
     ],
     include_dirs=[HIP_DIR],
     extra_compile_args={
